@@ -14,8 +14,20 @@ metric = training INPUT voxels per second (the reference's own definition,
 training/trainer.py:283-284), whole job.  roofline: fp32-MFMA; achieved =
 algorithmic fwd+bwd FLOPs per step (118.29 GF for this
 workload) / mean step time measured with HIP events on the plan's stream.
-cpu_baseline: the torch-CPU fp32 port of the same step (oracle/torch_step.py)
-on this box's host cores, rank 0, N=1 only.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the
+outputs (--dump-outputs DIR), the line.  --full adds what rides along: the CPU baseline
+(the torch-CPU fp32 port of the same step, oracle/torch_step.py, on the host's cores,
+rank 0, N=1 only), the other three training nets in the same line (lite183 at N=1,
+roofline.also) and the recorded profile figures (roofline.traffic / mfma_util).
+
+--dump-outputs DIR: after the timed steps, what the timed path computes, as DIR/<name>.npy
+(float32).  Training workloads: the loss and every trainable parameter after the update of
+ONE more step of the same path, taken from the initial state (initial parameters, zero Adam
+moments) -- the weight gradients sum with float atomics, so the state the timed steps leave
+differs between runs in the last bits and Adam amplifies that; from the shared initial state
+two runs agree to rounding.  Other workloads: the last prediction or patch.  The inputs
+depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -101,6 +113,34 @@ def recorded_profile(workload):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(dirname, arrays):
+    """write {name: array} as dirname/<name>.npy in float32, at most DUMP_BUDGET_BYTES in all:
+    over budget, every large array is replaced by a fixed, seeded sample of its flat elements
+    (the same indices in every run with the same arguments)"""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float32)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        scale = 0.95 * DUMP_BUDGET_BYTES / total
+        for i, k in enumerate(sorted(arrays)):
+            a = arrays[k]
+            keep = max(4096, int(a.size * scale))
+            if a.size > keep:
+                # (sorted, de-duplicated seeded draws: no permutation of the whole array)
+                idx = np.unique(np.random.RandomState(1000 + i).randint(0, a.size, keep))
+                arrays[k] = a.reshape(-1)[idx]
+        assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
 def algorithmic_gflop(model):
     """2*MAC per Conv node (``computational_cost`` = MACs, neural.py:767-778); wgrad = dgrad =
     fwd; no dgrad for the layer that reads the raw input."""
@@ -161,15 +201,17 @@ def dense_prediction_bench(args, rank, world):
         model = nets.neuro3d_lite((None, 1) + sp)
     rng = np.random.RandomState(0)
     raw = rng.rand(1, 43, 331, 331).astype(np.float32)
-    for _ in range(max(1, min(args.warmup, 2))):
+    for _ in range(args.warmup):
         pred = model.predict_dense(raw)
-    steps = max(1, min(args.steps, 5))
+    steps = args.steps
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
         pred = model.predict_dense(raw)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"prediction": pred})
     peak = PEAK_BF16_MFMA_TFLOPS if args.mfma == "bf16" else PEAK_FP32_MFMA_TFLOPS
     if mfp:
         fwd_gf = sum(2.0 * n.computational_cost for n in model.nodes.values()
@@ -212,7 +254,9 @@ def dense_unet_bench(args, rank, world):
     raw = rng.rand(1, 512, 512, 512).astype(np.float32)
     osp = tuple(model.prediction_node.shape.spatial_shape)
     model.predict_dense(raw[:, :patch[0], :patch[1], :patch[2] + osp[2]])   # compile (+ tune): 2 tiles
-    steps = max(1, min(args.steps, 2))
+    for _ in range(args.warmup):
+        model.predict_dense(raw)
+    steps = args.steps
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
@@ -221,6 +265,8 @@ def dense_unet_bench(args, rank, world):
     dt = (time.perf_counter() - t0) / steps
     assert pred.shape == (2, 424, 424, 424), pred.shape
     assert np.isfinite(pred).all() and abs(float(pred.sum(0).mean()) - 1.0) < 1e-4
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"prediction": pred})
     # algorithmic forward FLOPs of one tile (SURVEY.md 8d convention): 2 * MAC per Conv; an
     # UpConv at its useful cost 2 * Cout * Cin * N_out (its computational_cost counts the
     # zero-stuffed dense form the CPU reference executes, prod(pool) times that)
@@ -230,7 +276,7 @@ def dense_unet_bench(args, rank, world):
     n_tiles = int(np.prod([-(-424 // o) for o in osp]))
     peak = PEAK_BF16_MFMA_TFLOPS if args.mfma == "bf16" else PEAK_FP32_MFMA_TFLOPS
     out = {"metric": "dense_prediction_voxels_per_sec", "value": float(np.prod(pred.shape[1:])) / dt,
-           "unit": "voxels/s", "n_gpus": 1, "steps": steps, "warmup": 1,
+           "unit": "voxels/s", "n_gpus": 1, "steps": steps, "warmup": args.warmup,
            "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": args.mfma, "data": "synthetic",
            "config": {"workload": "unet3d (examples/unet3d.py) predict_dense (1,512,512,512)->"
@@ -260,10 +306,10 @@ def warp_bench(args, rank, world):
     smp = PatchSampler([vol], [lab], ps, strides, offsets, seed=0)
     kw = dict(grey_augment_channels=[0], warp=True, warp_args={'sample_aniso': True,
                                                                'perspective': True})
-    for _ in range(max(args.warmup, 3)):
+    for _ in range(args.warmup):
         smp.getbatch(1, 'train', **kw)
     ctx = get_ctx()
-    steps = max(args.steps, 20)
+    steps = args.steps
     torch.cuda.synchronize()
     e0, e1 = ctx.event(), ctx.event()
     t0 = time.perf_counter()
@@ -274,6 +320,8 @@ def warp_bench(args, rank, world):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     dev_ms = ctx.elapsed_ms(e0, e1) / steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"patch": _host(d), "target": _host(t)})
     vox = float(np.prod(ps)) + float(np.prod(smp.target_ps))
     out = {"metric": "augmented_patches_per_sec", "value": 1.0 / dt, "unit": "patches/s",
            "n_gpus": 1, "steps": steps, "warmup": args.warmup, "ms_per_step": dt * 1e3,
@@ -286,7 +334,7 @@ def warp_bench(args, rank, world):
            "roofline": {"bound": "hbm", "achieved": 8.0 * vox / (dev_ms * 1e-3) / 1e9, "peak": 8000.0,
                         "unit": "GB/s", "frac": 8.0 * vox / (dev_ms * 1e-3) / 1e9 / 8000.0,
                         "traffic": None, "device_ms_per_patch": dev_ms}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import warp_oracle as WO
         g = np.random.RandomState(1)
         ts = []
@@ -397,10 +445,11 @@ def selftest_bench(args, rank, world):
                           "config": {"workload": "selftest (no GPU)", "ranks": ranks}})
 
 
-def time_training(workload, args, rank, world, dev, steps, warmup):
+def time_training(workload, args, rank, world, dev, steps, warmup, dump=False):
     """Build the workload's net, capture its training step and time `steps` steps of it after
     `warmup` untimed ones (barrier + synchronize on both sides; HIP events on the plan's
-    stream for the device time).  Inputs wait in HBM before the timed region starts."""
+    stream for the device time).  Inputs wait in HBM before the timed region starts.
+    ``dump``: afterwards, one more step from the initial state -> r["outputs"] (see below)."""
     from elektronn2_amd import parallel, nets
     from elektronn2_amd import neuromancer as nm
     builder, sp, gf_table = WORKLOADS[workload]
@@ -413,6 +462,8 @@ def time_training(workload, args, rank, world, dev, steps, warmup):
     else:
         gflop = algorithmic_gflop(model)
     params0 = conv_params(model)              # initial weights, for the CPU baseline leg
+    init = ({k: p.get_value() for k, p in model.loss_node.all_trainable_params.items()}
+            if dump else None)
     model.set_opt_meta_params('Adam', dict(lr=5e-4, mom=0.9, beta2=0.999, wd=0.5e-4))
     opt = model.optimisers['Adam']
     opt.step.compile()
@@ -509,8 +560,26 @@ def time_training(workload, args, rank, world, dev, steps, warmup):
         # every timed step took a batch and left a loss: the ring and the history counted them
         hist = plan.loss_history(min(steps, 256))
         assert np.isfinite(hist).all() and abs(float(hist[-1]) - loss) <= 1e-6 * abs(loss), (hist[-3:], loss)
+    outputs = None
+    if dump:
+        # The weight gradients sum with float atomics, so the state the timed steps leave
+        # differs from run to run in the last bits, and Adam carries that from step to step.
+        # What is dumped is ONE more step of the same path from a state every run shares:
+        # the initial parameters, zero moments, t = 0, the batch the next step takes (the
+        # ring / staged batches depend on the arguments only).  It gives what a caller of
+        # the training step receives: the loss and the updated parameters.
+        for k, p in model.loss_node.all_trainable_params.items():
+            p.set_value(init[k])              # (the plan repacks its weight images before the step)
+        n = opt.momentum.numel()
+        opt.load_state_dict({'m': np.zeros(n, np.float32), 's': np.zeros(n, np.float32), 't': 0.0})
+        torch.cuda.synchronize()
+        advance(1)
+        torch.cuda.synchronize()
+        outputs = {"loss": np.array([plan.scratch[model.loss_node.parent[0], 'loss'].item()], np.float32)}
+        for k, p in model.loss_node.all_trainable_params.items():
+            outputs["param_" + k] = p.get_value()
     return dict(builder=builder, sp=sp, osp=osp, gflop=gflop, params0=params0, model=model,
-                plan=plan, xs=xs, ts=ts, dt=dt, dev_ms=dev_ms, loss=loss, kpl=kpl)
+                plan=plan, xs=xs, ts=ts, dt=dt, dev_ms=dev_ms, loss=loss, kpl=kpl, outputs=outputs)
 
 
 _REAL_STDOUT = None
@@ -541,16 +610,23 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="lite183", choices=sorted(WORKLOADS) + ["dense183", "dense183mfp", "dense512unet", "warp183", "selftest"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, the "
+                         "other training nets (lite183 at N = 1: roofline.also), the recorded "
+                         "profile figures (roofline.traffic / mfma_util)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--steps-per-launch", type=int, default=int(os.environ.get("E2_STEPS_PER_LAUNCH", "10")),
                     help="training steps per graph launch at N = 1 (Plan.run_steps: batches from a "
                          "device-side ring, losses into a device-side history); 1 = one launch per step")
     ap.add_argument("--no-also", action="store_true",
-                    help="lite183 at N = 1 also times neuro3d@185 and the two U-Nets "
+                    help="with --full, lite183 at N = 1 also times neuro3d@185 and the two U-Nets "
                          "(roofline.also.<workload>); skip them")
     ap.add_argument("--also", default="full185,unet_lite140,unet132",
-                    help="the workloads that ride along in the default N = 1 line")
+                    help="the workloads that ride along in the --full N = 1 line")
     ap.add_argument("--exchange-at-1", action="store_true",
                     help="N = 1 only, not the headline: run the data-parallel form of the step "
                          "(segmented graphs + the RCCL all-reduces) over a ONE-rank nccl group -- "
@@ -562,6 +638,8 @@ def main():
                          "bf16 operands with f32 sums (SURVEY.md 8f-3; a separate, looser-"
                          "tolerance path -- never the headline number)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.sources_sha:
         print(sources_sha16())
         return
@@ -614,9 +692,12 @@ def main():
         return warp_bench(args, rank, world)
     backend_name = torch.distributed.get_backend() if torch.distributed.is_initialized() else None
     dev = torch.device("cuda", parallel.local_device(backend_name))
-    r = time_training(args.workload, args, rank, world, dev, args.steps, args.warmup)
+    r = time_training(args.workload, args, rank, world, dev, args.steps, args.warmup,
+                      dump=bool(args.dump_outputs))
     builder, sp, osp, gflop = r["builder"], r["sp"], r["osp"], r["gflop"]
     plan, dt, dev_ms, loss = r["plan"], r["dt"], r["dev_ms"], r["loss"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r["outputs"])
 
     ranks = None
     if world > 1:
@@ -643,7 +724,9 @@ def main():
     value = vox_per_step * args.steps / dt
     achieved = gflop / (dev_ms * 1e-3) / 1e3            # TFLOP/s per GPU
     peak = PEAK_BF16_MFMA_TFLOPS if bf16 else PEAK_FP32_MFMA_TFLOPS
-    prof = recorded_profile(args.workload)
+    # the recorded PMC figures are not measured in this run: --full only
+    prof = (recorded_profile(args.workload) if args.full else
+            {"traffic": None, "mfma_util": None, "profile": None, "profile_stale": None})
     out = {
         "metric": "training_input_voxels_per_sec",
         "value": value,
@@ -683,8 +766,8 @@ def main():
     }
     # what the CPU leg needs, on the host -- then the headline plan's graphs, arena and staged
     # batches are released before any further net is built
-    cpu_in = (r["xs"][0].cpu().numpy(), r["ts"][0].cpu().numpy(), r["params0"])
-    if (world == 1 and args.workload == "lite183" and not args.no_also and not bf16
+    cpu_in = (r["xs"][0].cpu().numpy(), r["ts"][0].cpu().numpy(), r["params0"]) if args.full else None
+    if (args.full and world == 1 and args.workload == "lite183" and not args.no_also and not bf16
             and not args.exchange_at_1):
         # The net the target NAMES (north_star: ">= 50 % MFMA roofline on the neuro3d 3D-conv
         # fwd+bwd", examples/neuro3d.py:51-63) and BASELINE configs 3 and 5 (examples/
@@ -719,7 +802,7 @@ def main():
                 out["roofline"]["also"][wl] = {"error": "%s: %s" % (type(e).__name__, e)}
     if builder in ("unet3d_lite", "unet3d"):
         args.no_cpu_baseline = True           # the CPU leg is the sequential-net port
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         x, t, params0 = cpu_in
         # the ONLY use of oracle/ in this script: the CPU port, timed as the baseline
         from oracle import e2_oracle as O

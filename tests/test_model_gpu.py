@@ -3,6 +3,10 @@ the CPU oracle: loss, every dL/dw and dL/db, parameters after 1 and 3 Adam steps
 (lr=5e-4, mom=0.9, beta2=0.999, wd=5e-5: examples/neuro3d.py:33-39).
 Tolerance 1e-4 relative (BASELINE.json north_star), measured against the
 largest magnitude of each tensor."""
+import contextlib
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -22,6 +26,41 @@ def rel(a, b):
     a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
     assert a.shape == b.shape, (a.shape, b.shape)
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+SIDE_STREAM_TILINGS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                   "side_stream_tilings.json")
+
+
+@contextlib.contextmanager
+def table_entries(path):
+    """the tuning table's entries of a fixture file hold inside the block (no tuning on first
+    sight for those problems); the table is restored afterwards.  Inside the block the table is
+    saved to a scratch file (E2HIP_TUNE_CACHE), so the fixture never reaches the user's cache."""
+    import tempfile
+    from elektronn2_amd import autotune
+    with open(path) as f:
+        entries = json.load(f)
+    table = autotune._load()
+    old = {k: table.get(k) for k in entries}
+    env = os.environ.get("E2HIP_TUNE_CACHE")
+    scratch = tempfile.mkdtemp(prefix="e2_tune_")
+    os.environ["E2HIP_TUNE_CACHE"] = os.path.join(scratch, "tune_cache.json")
+    table.update(entries)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                table.pop(k, None)
+            else:
+                table[k] = v
+        if env is None:
+            os.environ.pop("E2HIP_TUNE_CACHE", None)
+        else:
+            os.environ["E2HIP_TUNE_CACHE"] = env
+        import shutil
+        shutil.rmtree(scratch, ignore_errors=True)
 
 
 def build(spec_name, sp, params):
@@ -479,8 +518,18 @@ def test_weight_gradients_on_the_side_stream_in_f32_mode():
     """Per-problem side-stream flags (autotune.side_flag / plan option side_mask; DESIGN finding
     56): in f32 mode the plan keeps one stream, except for the weight gradients the tuning table
     marks -- their launches form a side branch of the captured graph, issued behind the main
-    stream's next launches (side_defer).  Any choice of layers gives the losses and parameters of
-    the single-stream plan (to the weight gradients' atomic order); eager, capture, replay."""
+    stream's next launches (side_defer).  Any choice of layers gives the gradients of the
+    single-stream plan to the weight gradients' atomic order (eager and replayed), and its
+    losses and parameters over four Adam steps; eager, capture, replay.
+
+    Four Adam steps can take one of two paths that last-bit atomic noise selects between (a
+    discrete decision -- relu / pooling -- flips): the single-stream plan against ITSELF (graph
+    against eager) ends 2.9e-5 apart on some runs and 1e-7 on others, the gradients 3e-7 apart
+    either way, with or without side branches.  How far apart the two paths end depends on the
+    tilings (up to 1.9e-4 seen with tilings tuned on the fly), so the problems of this test
+    (neuro3d at (17,109,109), not in the shipped table) run with the tilings of
+    tests/golden/side_stream_tilings.json (tuned on an MI355X) instead of being timed on first
+    sight."""
     from elektronn2_amd.neuromancer import plan_options
     spec, sp = O.NEURO3D, (17, 109, 109)
     params = O.init_net(spec, 1, seed=7)
@@ -489,14 +538,23 @@ def test_weight_gradients_on_the_side_stream_in_f32_mode():
     t = rng.randint(0, 2, (1, 1) + O.net_out_shape(spec, sp)).astype(np.float32)
     res = {}
     for mask in (0, 465, 511, 2):
-        with plan_options(side_mask=mask, side_table=False):
+        with plan_options(side_mask=mask, side_table=False), table_entries(SIDE_STREAM_TILINGS):
             m = build('full', sp, params)
+            grads = [[np.array(g) for g in m.gradients(x, t)] for _ in range(2)]   # eager, replay
+            gplan = m._grad_func.func
+            gforced = [n.name for n in gplan._side_order or [] if gplan.side_forced(n)]
             losses = [float(m.trainingstep(x, t, optimiser='Adam')[0]) for _ in range(4)]
             plan = m.optimisers['Adam'].step.func
             assert not plan.use_side
             forced = [n.name for n in plan._side_order or [] if plan.side_forced(n)]
             assert len(forced) == bin(mask).count("1"), (mask, forced)
-            res[mask] = (losses, [q.get_value() for q in m.loss_node.all_trainable_params.values()])
+            assert gforced == forced, (mask, gforced, forced)
+            res[mask] = (losses, [q.get_value() for q in m.loss_node.all_trainable_params.values()],
+                         grads)
+    for mask in (0, 465, 511, 2):
+        for gs in res[mask][2]:
+            for a, b in zip(gs, res[0][2][0]):
+                assert rel(a, b) < 1e-5, (mask, rel(a, b))
     for mask in (465, 511, 2):
         for a, b in zip(res[mask][0], res[0][0]):
             assert abs(a - b) < 1e-5 * abs(b), (mask, res[mask][0], res[0][0])

@@ -6,7 +6,7 @@ O=gpurun_out/${1:-collect}
 mkdir -p $O
 run() { # name, args...
   n=$1; shift
-  timeout -k 10 600 python bench.py "$@" > $O/$n.json 2> $O/$n.err || { echo "$n FAILED"; tail -5 $O/$n.err; return; }
+  timeout -k 10 600 python bench.py --full "$@" > $O/$n.json 2> $O/$n.err || { echo "$n FAILED"; tail -5 $O/$n.err; return; }
   python - <<PY
 import json
 d = json.load(open("$O/$n.json"))
@@ -24,8 +24,8 @@ run unet_lite140_bf16 --workload unet_lite140 --mfma bf16
 run unet132_bf16 --workload unet132 --mfma bf16
 run dense183 --workload dense183
 run dense183mfp --workload dense183mfp
-run dense512unet --workload dense512unet --steps 1
-run dense512unet_bf16 --workload dense512unet --steps 1 --mfma bf16
+run dense512unet --workload dense512unet --steps 1 --warmup 0
+run dense512unet_bf16 --workload dense512unet --steps 1 --warmup 0 --mfma bf16
 run warp183 --workload warp183
 timeout -k 10 300 python tools/soak.py 2000 > $O/soak_sync.txt 2>&1; tail -2 $O/soak_sync.txt
 timeout -k 10 300 python tools/soak.py 2000 --async > $O/soak_async.txt 2>&1; tail -2 $O/soak_async.txt

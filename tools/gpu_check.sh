@@ -1,7 +1,7 @@
 #!/bin/bash
 # The standard GPU check of a change (run on the GPU box via gpurun):
 #   tools/gpu_check.sh <tag> [notests] [workloads...]      default workloads: lite183 full185
-# 1. pytest -m gpu (unless `notests`)  2. the driver's bench line (python bench.py)
+# 1. pytest -m gpu (unless `notests`)  2. the full bench line (python bench.py --full)
 # 3. per workload: rocprofv3 kernel stats of `bench.py --workload W --steps 20 --warmup 5`
 #    -> gpurun_out/<tag>/kernel_stats_<W>.csv, diffed against the profile of record
 #    (tools/kstats_diff.py; a regression is REPORTED here, adopt_profile.py refuses it)
@@ -13,7 +13,7 @@ if [ "$1" == "notests" ]; then shift; else
   timeout -k 10 900 python -m pytest -m gpu -q -x --durations=10 tests > $O/pytest_gpu.log 2>&1 || { tail -40 $O/pytest_gpu.log; exit 1; }
   tail -3 $O/pytest_gpu.log
 fi
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/bench.json"))

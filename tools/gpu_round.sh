@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 O=gpurun_out/$T
 mkdir -p $O
 python bench.py --sources-sha > $O/sources_sha16.txt
-timeout -k 10 400 python bench.py --workload $W > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --workload $W --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --workload $W --steps 20 --warmup 5 --no-cpu-baseline --no-also > $O/bench_prof.json 2> $O/prof.err || { tail -20 $O/prof.err; exit 1; }
 cp $(find $O/prof -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv && rm -rf $O/prof
