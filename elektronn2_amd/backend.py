@@ -57,6 +57,13 @@ def bf16_dst(cl=None, cl_dims=None, cl_off=(0, 0, 0), pl=None, pl_plane=0, pl_pi
     return d
 
 
+class NllWeights(C.Structure):
+    """e2_nll_weights (include/e2hip.h): class / example weights and the lazy-labelling masks of
+    the weighted MultinoulliNLL; null members take their default"""
+    _fields_ = [("class_w", C.c_void_p), ("example_w", C.POINTER(Tensor5)),
+                ("labelled", C.c_void_p), ("not_present", C.c_void_p)]
+
+
 def t5_shape(shape):
     """a Tensor5 that carries extents only (null pointer): the shape argument of the entry points
     whose operand was made ahead of the call"""
@@ -72,6 +79,7 @@ def _load():
             "`make -C elektronn2_amd/csrc`.  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     P5 = C.POINTER(Tensor5)
+    PW = C.POINTER(NllWeights)
     vp, i, sz, fp = C.c_void_p, C.c_int, C.c_size_t, C.c_void_p
     sig = {
         "e2_ctx_create": (C.c_int, [i, C.POINTER(vp)]),
@@ -145,6 +153,13 @@ def _load():
         "e2_fill": (C.c_int, [vp, fp, sz, C.c_float]),
         "e2_softmax_nll_fwd": (C.c_int, [vp, P5, P5, P5, fp]),
         "e2_softmax_nll_bwd": (C.c_int, [vp, P5, P5, fp, P5, fp]),
+        "e2_softmax_nll_fwd_w": (C.c_int, [vp, P5, P5, P5, fp, PW]),
+        "e2_softmax_nll_bwd_w": (C.c_int, [vp, P5, P5, fp, P5, fp, PW]),
+        "e2_head_fwd_w": (C.c_int, [vp, P5, fp, fp, i, P5, P5, fp, PW]),
+        "e2_head_bwd_w": (C.c_int, [vp, P5, fp, P5, P5, fp, P5, i, fp, fp, fp, C.c_void_p,
+                                    sz, PW]),
+        "e2_tail_fwd_bwd_w": (C.c_int, [vp, P5, fp, fp, fp, i, fp, fp, i, P5, P5, P5, P5, i, P5,
+                                        fp, fp, C.c_void_p, sz, C.POINTER(C.c_int), PW]),
         "e2_malis_nll": (C.c_int, [vp, P5, fp, fp, fp, P5, fp]),
         "e2_fill_multi": (C.c_int, [vp, vp, vp, C.c_int, C.c_float]),
         "e2_set_skip_zero_fill": (C.c_int, [vp, C.c_int]),
@@ -237,6 +252,21 @@ def t5(t: torch.Tensor) -> Tensor5:
         raise TypeError("innermost stride must be 1, got %s" % (s,))
     return Tensor5(t.data_ptr(), t.shape[0], t.shape[1], t.shape[2], t.shape[3],
                    t.shape[4], s[0], s[1], s[2], s[3])
+
+
+def nll_weights(class_w=None, example_w=None, labelled=None, not_present=None):
+    """an e2_nll_weights descriptor of device tensors: ``class_w`` (ncls,), ``example_w``
+    (n, 1, d, h, w), ``labelled`` / ``not_present`` (n, ncls); None = the default.  The kernels
+    read the tensors when they RUN: a captured launch follows later changes of their contents."""
+    w = NllWeights()
+    w._keep = (class_w, example_w, labelled, not_present)       # (the tensors outlive the descriptor)
+    w.class_w = _fp(class_w)
+    if example_w is not None:
+        w._ew = t5(example_w)
+        w.example_w = C.pointer(w._ew)
+    w.labelled = _fp(labelled)
+    w.not_present = _fp(not_present)
+    return w
 
 
 def _fp(t: Optional[torch.Tensor]):
@@ -403,11 +433,15 @@ class Context:
     def head_supported(cin, ncls):
         return bool(_lib.e2_head_supported(int(cin), int(ncls)))
 
-    def head_fwd(self, x, w, bias, target, probs, stats):
-        _chk(_lib.e2_head_fwd(self.h, C.byref(t5(x)), _fp(w), _fp(bias), probs.shape[1],
-                              C.byref(t5(target)) if target is not None else None,
-                              C.byref(t5(probs)), _fp(stats) if stats is not None else None),
-             "e2_head_fwd")
+    def head_fwd(self, x, w, bias, target, probs, stats, weights=None):
+        """``weights``: an ``nll_weights`` descriptor -> the weighted loss (e2_head_fwd_w)"""
+        args = (self.h, C.byref(t5(x)), _fp(w), _fp(bias), probs.shape[1],
+                C.byref(t5(target)) if target is not None else None,
+                C.byref(t5(probs)), _fp(stats) if stats is not None else None)
+        if weights is None:
+            _chk(_lib.e2_head_fwd(*args), "e2_head_fwd")
+        else:
+            _chk(_lib.e2_head_fwd_w(*(args + (C.byref(weights),))), "e2_head_fwd_w")
 
     @staticmethod
     def head_bwd_ws_bytes(x_shape, ncls):
@@ -415,16 +449,20 @@ class Context:
         return int(_lib.e2_head_bwd_workspace_bytes(n, cin, int(ncls), d, h, w))
 
     def head_bwd(self, x, w, probs, target, stats, dx, accumulate_dx, dw, dbias, loss_out,
-                 ws=None):
+                 ws=None, weights=None):
         if ws is None:
             ws = torch.empty(self.head_bwd_ws_bytes(x.shape, probs.shape[1]) // 4 + 16,
                              dtype=torch.float32, device=self.device)
-        _chk(_lib.e2_head_bwd(self.h, C.byref(t5(x)), _fp(w), C.byref(t5(probs)),
-                              C.byref(t5(target)), _fp(stats),
-                              C.byref(t5(dx)) if dx is not None else None,
-                              1 if accumulate_dx else 0, _fp(dw), _fp(dbias),
-                              _fp(loss_out) if loss_out is not None else None,
-                              C.c_void_p(ws.data_ptr()), ws.numel() * 4), "e2_head_bwd")
+        args = (self.h, C.byref(t5(x)), _fp(w), C.byref(t5(probs)),
+                C.byref(t5(target)), _fp(stats),
+                C.byref(t5(dx)) if dx is not None else None,
+                1 if accumulate_dx else 0, _fp(dw), _fp(dbias),
+                _fp(loss_out) if loss_out is not None else None,
+                C.c_void_p(ws.data_ptr()), ws.numel() * 4)
+        if weights is None:
+            _chk(_lib.e2_head_bwd(*args), "e2_head_bwd")
+        else:
+            _chk(_lib.e2_head_bwd_w(*(args + (C.byref(weights),))), "e2_head_bwd_w")
 
     # ---- the tail of the neuro3d nets: 1x1x1 conv + head, forward and backward --------
     @staticmethod
@@ -437,21 +475,25 @@ class Context:
         return int(_lib.e2_tail_workspace_bytes(n, c1, int(c2), int(ncls), d, h, w))
 
     def tail_fwd_bwd(self, x, wp_fwd, wp_dgrad, bias1, w_head, b_head, target, probs, dpre, dx,
-                     stats, ws, gm_mode=0, gm_src=None, gm_bias=None):
+                     stats, ws, gm_mode=0, gm_src=None, gm_bias=None, weights=None):
         """csrc/tail.hip: forward and backward of [1x1x1 conv + bias + relu] -> [classifier
         head] in one launch; returns the number of partial-sum slots written to ``ws``.
         ``gm_mode``: dx goes through the activation backward of the layer that produced x
         (1: slope from ``gm_src`` = its activated output, 2: from ``gm_src`` = its
-        pre-activation + ``gm_bias``, 3: linear) and that layer's bias gradient joins the slots"""
+        pre-activation + ``gm_bias``, 3: linear) and that layer's bias gradient joins the slots.
+        ``weights``: an ``nll_weights`` descriptor -> the weighted loss (e2_tail_fwd_bwd_w)"""
         n_slots = C.c_int(0)
-        _chk(_lib.e2_tail_fwd_bwd(self.h, C.byref(t5(x)), _fp(wp_fwd), _fp(wp_dgrad), _fp(bias1),
-                                  dpre.shape[1], _fp(w_head), _fp(b_head), probs.shape[1],
-                                  C.byref(t5(target)), C.byref(t5(probs)), C.byref(t5(dpre)),
-                                  C.byref(t5(dx)) if dx is not None else None, int(gm_mode),
-                                  C.byref(t5(gm_src)) if gm_src is not None else None,
-                                  _fp(gm_bias), _fp(stats),
-                                  C.c_void_p(ws.data_ptr()), ws.numel() * 4, C.byref(n_slots)),
-             "e2_tail_fwd_bwd")
+        args = (self.h, C.byref(t5(x)), _fp(wp_fwd), _fp(wp_dgrad), _fp(bias1),
+                dpre.shape[1], _fp(w_head), _fp(b_head), probs.shape[1],
+                C.byref(t5(target)), C.byref(t5(probs)), C.byref(t5(dpre)),
+                C.byref(t5(dx)) if dx is not None else None, int(gm_mode),
+                C.byref(t5(gm_src)) if gm_src is not None else None,
+                _fp(gm_bias), _fp(stats),
+                C.c_void_p(ws.data_ptr()), ws.numel() * 4, C.byref(n_slots))
+        if weights is None:
+            _chk(_lib.e2_tail_fwd_bwd(*args), "e2_tail_fwd_bwd")
+        else:
+            _chk(_lib.e2_tail_fwd_bwd_w(*(args + (C.byref(weights),))), "e2_tail_fwd_bwd_w")
         return int(n_slots.value)
 
     def tail_reduce(self, ws, n_slots, c2, ncls, dw_head, db_head, db1, stats, loss_out,
@@ -626,14 +668,21 @@ class Context:
              "e2_fill")
 
     # ---- loss / optimiser ----------------------------------------------------------
-    def softmax_nll_fwd(self, logits, target, probs, stats):
-        _chk(_lib.e2_softmax_nll_fwd(self.h, C.byref(t5(logits)), C.byref(t5(target)),
-                                     C.byref(t5(probs)), _fp(stats)), "e2_softmax_nll_fwd")
+    def softmax_nll_fwd(self, logits, target, probs, stats, weights=None):
+        """``weights``: an ``nll_weights`` descriptor -> the weighted loss (the _w entry points)"""
+        args = (self.h, C.byref(t5(logits)), C.byref(t5(target)), C.byref(t5(probs)), _fp(stats))
+        if weights is None:
+            _chk(_lib.e2_softmax_nll_fwd(*args), "e2_softmax_nll_fwd")
+        else:
+            _chk(_lib.e2_softmax_nll_fwd_w(*(args + (C.byref(weights),))), "e2_softmax_nll_fwd_w")
 
-    def softmax_nll_bwd(self, probs, target, stats, dlogits, loss_out):
-        _chk(_lib.e2_softmax_nll_bwd(self.h, C.byref(t5(probs)), C.byref(t5(target)),
-                                     _fp(stats), C.byref(t5(dlogits)), _fp(loss_out)),
-             "e2_softmax_nll_bwd")
+    def softmax_nll_bwd(self, probs, target, stats, dlogits, loss_out, weights=None):
+        args = (self.h, C.byref(t5(probs)), C.byref(t5(target)), _fp(stats),
+                C.byref(t5(dlogits)), _fp(loss_out))
+        if weights is None:
+            _chk(_lib.e2_softmax_nll_bwd(*args), "e2_softmax_nll_bwd")
+        else:
+            _chk(_lib.e2_softmax_nll_bwd_w(*(args + (C.byref(weights),))), "e2_softmax_nll_bwd_w")
 
     def fill_multi(self, ptrs_dev, counts_dev, n, value=0.0):
         """one launch that fills n flat regions (int64 device tensors of pointers / counts)"""

@@ -67,6 +67,38 @@ void e2_set_error(const char* fmt, ...);
     }                                                                        \
   } while (0)
 
+// e2_nll_weights as the loss kernels take it (pointwise.hip, head.hip, tail.hip): null = default
+struct NllW {
+  const float* cw;                  // class weights [ncls]
+  const float* lab;                 // mask_class_labeled [n][ncls]
+  const float* npr;                 // mask_class_not_present [n][ncls]
+  const float* ew;                  // example weights (n, 1, d, h, w)
+  long esN, esD, esH;
+};
+// One of the few floats behind an NllW pointer (class weights, masks): memory that no kernel of
+// the grid writes, read at a wave-uniform index.  Through the constant address space, so that the
+// read is a scalar load -- once per wave, not per lane -- also behind the kernel's own stores
+// (hipcc cannot prove those do not alias a plain pointer and would issue a per-lane load).
+#ifdef __HIPCC__
+__device__ __forceinline__ float e2_uniform_ld(const float* p, int i) {
+  return ((const __attribute__((address_space(4))) float*)p)[i];
+}
+#endif
+
+static inline int e2i_nll_weights(const e2_nll_weights* w, const e2_tensor5* target,
+                                  const char* who, NllW* out) {
+  *out = NllW{};
+  if (!w) return 0;
+  out->cw = w->class_w; out->lab = w->labelled; out->npr = w->not_present;
+  if (const e2_tensor5* e = w->example_w) {
+    E2_REQUIRE(e->ptr && e->c == 1 && e->n == target->n && e->d == target->d &&
+                   e->h == target->h && e->w == target->w,
+               "%s: example_w must be (n,1,d,h,w) matching the target", who);
+    out->ew = e->ptr; out->esN = e->sn; out->esD = e->sd; out->esH = e->sh;
+  }
+  return 0;
+}
+
 static inline int e2_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t e2_cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

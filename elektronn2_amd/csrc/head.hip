@@ -15,9 +15,9 @@
 //             end), every thread writes its share of dx = W^T dlogits.
 // Bound: HBM (read C*S*4 B; backward also writes C*S*4 B).
 #include "common.hpp"
+#include "nll_w.hpp"
 #include <algorithm>
 
-#define E2_EPS_NLL 1e-5f
 #define E2_HEAD_MAXC 4
 
 namespace {
@@ -40,6 +40,10 @@ __device__ __forceinline__ float h_wave_sum(float v) {
   return v;
 }
 
+// The kernel bodies are head_fwd_body.hpp / head_bwd_body.hpp, each compiled twice: with WT = false
+// as head_fwd_kernel / head_bwd_kernel and with WT = true (the weighted loss, nll_w.hpp) as
+// head_fwd_w_kernel / head_bwd_w_kernel.  (Textual, not a shared __device__ function: passing the
+// views on changed the instructions hipcc emits for the unweighted kernels.)
 // ---- forward ---------------------------------------------------------------------
 // work-group = 64 positions x 4 channel quarters (one wave each): the positions of a
 // net's last layer are few (13,690 for C-lite@183), so the channel loop is split to
@@ -49,63 +53,18 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HView x, const float* __r
                                                        const float* __restrict__ bias,
                                                        HView tg, int has_target, HView pr,
                                                        float* __restrict__ stats) {
-  __shared__ float part[4][NC][64];
-  const int S = x.d * x.h * x.w;
-  const int p = threadIdx.x & 63, cq = threadIdx.x >> 6;
-  const int s = blockIdx.x * 64 + p;
-  const int n = blockIdx.z;
-  const bool valid = s < S;
-  int xx = 0, y = 0, z = 0;
-  if (valid) {
-    xx = s % x.w;
-    const int t = s / x.w;
-    y = t % x.h; z = t / x.h;
-  }
-  const int per = (x.c + 3) >> 2;
-  const int c0 = cq * per, c1 = min(c0 + per, x.c);
-  float acc[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) acc[c] = 0.f;
-  if (valid) {
-    const float* xp = x.p + hidx(x, n, z, y, xx);
-#pragma unroll 10
-    for (int ci = c0; ci < c1; ++ci) {
-      const float v = xp[(long)ci * x.sc];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) acc[c] = fmaf(w[c * x.c + ci], v, acc[c]);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < NC; ++c) part[cq][c][p] = acc[c];
-  __syncthreads();
-  if (cq != 0) return;
-  float lsum = 0.f, nlab = 0.f;
-  if (valid) {
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      acc[c] = ((part[0][c][p] + part[1][c][p]) + (part[2][c][p] + part[3][c][p])) + bias[c];
-      m = fmaxf(m, acc[c]);
-    }
-    float den = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) den += expf(acc[c] - m);
-    const float tv = has_target ? tg.p[hidx(tg, n, z, y, xx)] : -1.f;
-    float* pp = pr.p + hidx(pr, n, z, y, xx);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const float pc = expf(acc[c] - m) / den;
-      pp[(long)c * pr.sc] = pc;
-      if (tv == (float)c) { lsum -= logf(pc + E2_EPS_NLL); nlab += 1.f; }
-    }
-  }
-  if (has_target) {                       // wave 0 only
-    const float a = h_wave_sum(lsum), b = h_wave_sum(nlab);
-    if (p == 0) {
-      if (a != 0.f) unsafeAtomicAdd(stats + 0, a);
-      if (b != 0.f) unsafeAtomicAdd(stats + 1, b);
-    }
-  }
+  constexpr bool WT = false;
+  const NllW wt{};
+#include "head_fwd_body.hpp"
+}
+template <int NC>
+__global__ __launch_bounds__(256) void head_fwd_w_kernel(HView x, const float* __restrict__ w,
+                                                         const float* __restrict__ bias,
+                                                         HView tg, HView pr,
+                                                         float* __restrict__ stats, NllW wt) {
+  constexpr bool WT = true;
+  constexpr int has_target = 1;
+#include "head_fwd_body.hpp"
 }
 
 // ---- backward --------------------------------------------------------------------
@@ -120,124 +79,21 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HView x, const float* __r
                                                        float* __restrict__ loss_out,
                                                        int tilesPerN, int nTiles, int sum_mode,
                                                        float* __restrict__ count_out) {
-  extern __shared__ float hs[];
-  const int C = x.c;
-  float* dl = hs;                         // [NC][HT]
-  float* xs = hs + NC * HT;               // [C][HT + 1]
-  const int tid = threadIdx.x;
-  const int S = x.d * x.h * x.w;
-  float inv = 1.f / (stats[1] + E2_EPS_NLL);
-  if (blockIdx.x == 0 && tid == 0 && loss_out) loss_out[0] = stats[0] * inv;
-  if (blockIdx.x == 0 && tid == 0 && count_out) count_out[0] = stats[1];
-  if (sum_mode) inv = 1.f;                  // (e2_set_loss_grad_mode: unnormalised gradients)
-  // thread ci < C (two rounds when C > 256) owns dW[c][ci]
-  float aw[2][NC];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int c = 0; c < NC; ++c) aw[r][c] = 0.f;
-  float ab[NC];                           // dbias partials of threads 0..HT-1
-#pragma unroll
-  for (int c = 0; c < NC; ++c) ab[c] = 0.f;
-
-  for (int tile = blockIdx.x; tile < nTiles; tile += gridDim.x) {
-    const int n = tile / tilesPerN;
-    const int s0 = (tile - n * tilesPerN) * HT;
-    const int np = min(HT, S - s0);
-    // dlogits of the tile's positions
-    if (tid < HT) {
-      float d[NC];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) d[c] = 0.f;
-      if (tid < np) {
-        const int s = s0 + tid;
-        const int xx = s % x.w;
-        const int t = s / x.w;
-        const int y = t % x.h, z = t / x.h;
-        const float tv = tg.p[hidx(tg, n, z, y, xx)];
-        const float* pp = pr.p + hidx(pr, n, z, y, xx);
-        float pc[NC], pt = 0.f;
-        int tc = -1;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          pc[c] = pp[(long)c * pr.sc];
-          if (tv == (float)c) { tc = c; pt = pc[c]; }
-        }
-        // dL/dp_t = -inv/(p_t+eps);  dlogit_c = p_c*(dp_c - sum_k dp_k p_k)
-        const float gpt = (tc >= 0) ? (-inv / (pt + E2_EPS_NLL)) * pt : 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) d[c] = gpt * ((c == tc ? 1.f : 0.f) - pc[c]);
-      }
-#pragma unroll
-      for (int c = 0; c < NC; ++c) { dl[c * HT + tid] = d[c]; ab[c] += d[c]; }
-    }
-    // the input tile, coalesced: 256/HT channel rows of HT positions per pass
-    const int p = tid & (HT - 1);
-    int pz = 0, py = 0, px = 0;
-    if (p < np) {
-      const int s = s0 + p;
-      px = s % x.w;
-      const int t = s / x.w;
-      py = t % x.h; pz = t / x.h;
-    }
-    {
-      const long off = hidx(x, n, pz, py, px);
-      const bool pv = p < np;
-#pragma unroll 8
-      for (int ci = tid / HT; ci < C; ci += 256 / HT)
-        xs[ci * (HT + 1) + p] = pv ? x.p[off + (long)ci * x.sc] : 0.f;
-    }
-    __syncthreads();
-    // dW partial sums: thread = input channel
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int ci = tid + 256 * r;
-      if (ci < C) {
-        const float* row = xs + ci * (HT + 1);
-        for (int p = 0; p < HT; ++p) {
-          const float v = row[p];
-#pragma unroll
-          for (int c = 0; c < NC; ++c) aw[r][c] = fmaf(dl[c * HT + p], v, aw[r][c]);
-        }
-      }
-    }
-    // dx = W^T dlogits, written (or accumulated) coalesced
-    if (want_dx) {
-      if (p < np) {
-        float* dp = dx.p + hidx(dx, n, pz, py, px);
-        float d[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) d[c] = dl[c * HT + p];
-#pragma unroll 8
-        for (int ci = tid / HT; ci < C; ci += 256 / HT) {
-          float g = 0.f;
-#pragma unroll
-          for (int c = 0; c < NC; ++c) g = fmaf(w[c * C + ci], d[c], g);
-          float* q = dp + (long)ci * dx.sc;
-          *q = accumulate ? (*q + g) : g;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  // flush: this work-group's partial sums, part[block][NC*C + NC] (plain stores; 400+
-  // same-address atomics per address serialise for tens of microseconds)
-  float* mine = part + (long)blockIdx.x * (NC * C + NC);
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int ci = tid + 256 * r;
-    if (ci < C) {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) mine[c * C + ci] = aw[r][c];
-    }
-  }
-  if (tid < 64) {           // wave 0 (threads >= HT hold zeros)
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const float sb = h_wave_sum(ab[c]);
-      if (tid == 0) mine[NC * C + c] = sb;
-    }
-  }
+  constexpr bool WT = false;
+  const NllW wt{};
+#include "head_bwd_body.hpp"
+}
+template <int NC>
+__global__ __launch_bounds__(256) void head_bwd_w_kernel(HView x, const float* __restrict__ w,
+                                                         HView pr, HView tg,
+                                                         const float* __restrict__ stats,
+                                                         HView dx, int want_dx, int accumulate,
+                                                         float* __restrict__ part,
+                                                         float* __restrict__ loss_out,
+                                                         int tilesPerN, int nTiles, int sum_mode,
+                                                         float* __restrict__ count_out, NllW wt) {
+  constexpr bool WT = true;
+#include "head_bwd_body.hpp"
 }
 
 // dw[i] += sum_b part[b][i] (i < NC*C), dbias[c] += sum_b part[b][NC*C + c]
@@ -272,9 +128,9 @@ extern "C" int e2_head_supported(int cin, int ncls) {
 
 /* probs = softmax(W x + b) over the ncls channels; with a target also
  * stats[0] += sum(-log(p_target + 1e-5)), stats[1] += #labelled (zero stats first). */
-extern "C" int e2_head_fwd(e2_ctx* ctx, const e2_tensor5* x, const float* w, const float* bias,
-                           int ncls, const e2_tensor5* target, const e2_tensor5* probs,
-                           float* stats) {
+static int head_fwd_impl(e2_ctx* ctx, const e2_tensor5* x, const float* w, const float* bias,
+                         int ncls, const e2_tensor5* target, const e2_tensor5* probs,
+                         float* stats, const e2_nll_weights* wts) {
   E2_REQUIRE(ctx && w && bias, "head_fwd: null argument");
   if (int rc = head_check(x, "head_fwd x")) return rc;
   if (int rc = head_check(probs, "head_fwd probs")) return rc;
@@ -289,6 +145,18 @@ extern "C" int e2_head_fwd(e2_ctx* ctx, const e2_tensor5* x, const float* w, con
   const long S = (long)x->d * x->h * x->w;
   E2_REQUIRE(S < (1L << 31), "head_fwd: channel too large");
   dim3 grid((unsigned)((S + 63) / 64), 1, (unsigned)x->n);
+  if (wts) {
+    E2_REQUIRE(target, "head_fwd_w: the weighted loss needs a target");
+    NllW wt;
+    if (int rc = e2i_nll_weights(wts, target, "head_fwd_w", &wt)) return rc;
+#define E2_HFW(NC)                                                                       \
+  hipLaunchKernelGGL((head_fwd_w_kernel<NC>), grid, dim3(256), 0, ctx->stream, hv(x), w, \
+                     bias, vt, hv(probs), stats, wt)
+    if (ncls == 2) E2_HFW(2); else if (ncls == 3) E2_HFW(3); else E2_HFW(4);
+#undef E2_HFW
+    E2_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
 #define E2_HF(NC)                                                                      \
   hipLaunchKernelGGL((head_fwd_kernel<NC>), grid, dim3(256), 0, ctx->stream, hv(x), w, \
                      bias, vt, target ? 1 : 0, hv(probs), stats)
@@ -296,6 +164,21 @@ extern "C" int e2_head_fwd(e2_ctx* ctx, const e2_tensor5* x, const float* w, con
 #undef E2_HF
   E2_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+extern "C" int e2_head_fwd(e2_ctx* ctx, const e2_tensor5* x, const float* w, const float* bias,
+                           int ncls, const e2_tensor5* target, const e2_tensor5* probs,
+                           float* stats) {
+  return head_fwd_impl(ctx, x, w, bias, ncls, target, probs, stats, nullptr);
+}
+
+/* e2_head_fwd with the weighted loss (loss.py:261-347 with class_weights, example_weights,
+ * mask_class_labeled, mask_class_not_present): stats[0] += sum_up + sum_dn, stats[1] += n_tot
+ * (include/e2hip.h).  A target is required. */
+extern "C" int e2_head_fwd_w(e2_ctx* ctx, const e2_tensor5* x, const float* w, const float* bias,
+                             int ncls, const e2_tensor5* target, const e2_tensor5* probs,
+                             float* stats, const e2_nll_weights* wts) {
+  return head_fwd_impl(ctx, x, w, bias, ncls, target, probs, stats, wts);
 }
 
 static long head_grid(const e2_ctx* ctx, int n, long S) {
@@ -311,11 +194,11 @@ extern "C" size_t e2_head_bwd_workspace_bytes(int n, int cin, int ncls, int d, i
 /* gradients of loss = stats[0]/(stats[1]+1e-5): dx (optional; accumulate_dx: +=),
  * dw[ncls*cin] and dbias[ncls] are ACCUMULATED (zero them first); loss_out optional.
  * ws: e2_head_bwd_workspace_bytes(n, cin, ncls, d, h, w) bytes. */
-extern "C" int e2_head_bwd(e2_ctx* ctx, const e2_tensor5* x, const float* w,
-                           const e2_tensor5* probs, const e2_tensor5* target,
-                           const float* stats, const e2_tensor5* dx, int accumulate_dx,
-                           float* dw, float* dbias, float* loss_out, void* ws,
-                           size_t ws_bytes) {
+static int head_bwd_impl(e2_ctx* ctx, const e2_tensor5* x, const float* w,
+                         const e2_tensor5* probs, const e2_tensor5* target,
+                         const float* stats, const e2_tensor5* dx, int accumulate_dx,
+                         float* dw, float* dbias, float* loss_out, void* ws,
+                         size_t ws_bytes, const e2_nll_weights* wts) {
   E2_REQUIRE(ctx && w && stats && dw && dbias && ws, "head_bwd: null argument");
   if (int rc = head_check(x, "head_bwd x")) return rc;
   if (int rc = head_check(probs, "head_bwd probs")) return rc;
@@ -353,11 +236,51 @@ extern "C" int e2_head_bwd(e2_ctx* ctx, const e2_tensor5* x, const float* w,
                        accumulate_dx, part, loss_out, (int)tilesPerN, (int)nTiles,       \
                        ctx->loss_sum_mode, ctx->loss_count_out);                         \
   } while (0)
-  if (ncls == 2) E2_HB(2); else if (ncls == 3) E2_HB(3); else E2_HB(4);
+#define E2_HBW(NC)                                                                       \
+  do {                                                                                   \
+    static bool attr_done = false;                                                       \
+    if (!attr_done) {                                                                    \
+      E2_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&head_bwd_w_kernel<NC>), \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+      attr_done = true;                                                                  \
+    }                                                                                    \
+    hipLaunchKernelGGL((head_bwd_w_kernel<NC>), dim3(grid), dim3(256), lds, ctx->stream, \
+                       hv(x), w, hv(probs), hv(target), stats, vdx, dx ? 1 : 0,          \
+                       accumulate_dx, part, loss_out, (int)tilesPerN, (int)nTiles,       \
+                       ctx->loss_sum_mode, ctx->loss_count_out, wt);                     \
+  } while (0)
+  if (wts) {
+    NllW wt;
+    if (int rc = e2i_nll_weights(wts, target, "head_bwd_w", &wt)) return rc;
+    if (ncls == 2) E2_HBW(2); else if (ncls == 3) E2_HBW(3); else E2_HBW(4);
+  } else {
+    if (ncls == 2) E2_HB(2); else if (ncls == 3) E2_HB(3); else E2_HB(4);
+  }
 #undef E2_HB
+#undef E2_HBW
   E2_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(head_reduce_kernel, dim3(e2_cdiv(total, 256), std::min(grid, 16)), dim3(256),
                      0, ctx->stream, part, grid, total, ncls * x->c, dw, dbias);
   E2_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+extern "C" int e2_head_bwd(e2_ctx* ctx, const e2_tensor5* x, const float* w,
+                           const e2_tensor5* probs, const e2_tensor5* target,
+                           const float* stats, const e2_tensor5* dx, int accumulate_dx,
+                           float* dw, float* dbias, float* loss_out, void* ws,
+                           size_t ws_bytes) {
+  return head_bwd_impl(ctx, x, w, probs, target, stats, dx, accumulate_dx, dw, dbias, loss_out, ws,
+                       ws_bytes, nullptr);
+}
+
+/* e2_head_bwd for the weighted loss (loss.py:261-347; the gradient formula in include/e2hip.h):
+ * stats as e2_head_fwd_w left them */
+extern "C" int e2_head_bwd_w(e2_ctx* ctx, const e2_tensor5* x, const float* w,
+                             const e2_tensor5* probs, const e2_tensor5* target,
+                             const float* stats, const e2_tensor5* dx, int accumulate_dx,
+                             float* dw, float* dbias, float* loss_out, void* ws,
+                             size_t ws_bytes, const e2_nll_weights* wts) {
+  return head_bwd_impl(ctx, x, w, probs, target, stats, dx, accumulate_dx, dw, dbias, loss_out, ws,
+                       ws_bytes, wts);
 }

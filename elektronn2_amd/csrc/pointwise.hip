@@ -563,67 +563,41 @@ __global__ void ndhwc_to_ncdhw_kernel(const float* __restrict__ src, View5 dst) 
 // ---------------------------------------------------------------------------
 // channel softmax + MultinoulliNLL (sparse target), thread per position
 // ---------------------------------------------------------------------------
+// WT: the weighted form (e2_nll_weights; loss.py:172-212, 261-347), a compile-time variant: the
+// unweighted kernels are the WT = false bodies.  With L = mask_class_labeled, M =
+// mask_class_not_present, w = class weight, e = example weight:
+//   loss sum += -[t == c] L w e log(p_c + eps) - M w e log(q_c + eps),  count += [t == c] L
+// q_c = 1 - p_c is the sum of the OTHER classes' terms (f32 loses every digit of 1 - p_c where a
+// not-present class saturates).  The masks and class weights sit at work-group-uniform addresses
+// (scalar loads: e2_uniform_ld, common.hpp); the example weights are read next to the target.
+// S * sum(M), the not-present part of the count, is added once by one thread of the grid.  The
+// bodies are
+// softmax_nll_{fwd,bwd}_body.hpp, compiled twice each (textual: a shared __device__ function
+// changed the instructions of the unweighted kernels).
 __global__ void softmax_nll_fwd_kernel(View5 lg, View5 tg, View5 pr,
                                        float* __restrict__ stats) {
-  __shared__ float red[4];
-  const long S = (long)lg.d * lg.h * lg.w;
-  const long s = blockIdx.x * 256L + threadIdx.x;
-  const int n = blockIdx.z;
-  float lsum = 0.f, nlab = 0.f;
-  if (s < S) {
-    const int x = (int)(s % lg.w);
-    const long t = s / lg.w;
-    const int y = (int)(t % lg.h), z = (int)(t / lg.h);
-    const float* lp = lg.p + vidx(lg, n, 0, z, y, x);
-    float m = lp[0];
-    for (int c = 1; c < lg.c; ++c) m = fmaxf(m, lp[c * lg.sc]);
-    float den = 0.f;
-    for (int c = 0; c < lg.c; ++c) den += expf(lp[c * lg.sc] - m);
-    const float tv = tg.p[vidx(tg, n, 0, z, y, x)];
-    float* pp = pr.p + vidx(pr, n, 0, z, y, x);
-    for (int c = 0; c < lg.c; ++c) {
-      const float pc = expf(lp[c * lg.sc] - m) / den;
-      pp[c * pr.sc] = pc;
-      if (tv == (float)c) { lsum -= logf(pc + E2_EPS_NLL); nlab += 1.f; }
-    }
-  }
-  const float a = block_sum256(lsum, red);
-  const float b = block_sum256(nlab, red);
-  if (threadIdx.x == 0) {
-    if (a != 0.f) unsafeAtomicAdd(stats + 0, a);
-    if (b != 0.f) unsafeAtomicAdd(stats + 1, b);
-  }
+  constexpr bool WT = false;
+  const NllW wt{};
+#include "softmax_nll_fwd_body.hpp"
+}
+__global__ void softmax_nll_fwd_w_kernel(View5 lg, View5 tg, View5 pr,
+                                         float* __restrict__ stats, NllW wt) {
+  constexpr bool WT = true;
+#include "softmax_nll_fwd_body.hpp"
 }
 
 __global__ void softmax_nll_bwd_kernel(View5 pr, View5 tg, const float* __restrict__ stats,
                                        View5 dl, float* __restrict__ loss_out, int sum_mode,
                                        float* __restrict__ count_out) {
-  const long S = (long)pr.d * pr.h * pr.w;
-  const long s = blockIdx.x * 256L + threadIdx.x;
-  const int n = blockIdx.z;
-  float inv = 1.f / (stats[1] + E2_EPS_NLL);
-  if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) {
-    if (loss_out) loss_out[0] = stats[0] * inv;
-    if (count_out) count_out[0] = stats[1];
-  }
-  if (sum_mode) inv = 1.f;                  // (e2_set_loss_grad_mode: unnormalised gradients)
-  if (s >= S) return;
-  const int x = (int)(s % pr.w);
-  const long t = s / pr.w;
-  const int y = (int)(t % pr.h), z = (int)(t / pr.h);
-  const float tv = tg.p[vidx(tg, n, 0, z, y, x)];
-  const float* pp = pr.p + vidx(pr, n, 0, z, y, x);
-  float* dp = dl.p + vidx(dl, n, 0, z, y, x);
-  float pt = 0.f;
-  int tc = -1;
-  for (int c = 0; c < pr.c; ++c)
-    if (tv == (float)c) { tc = c; pt = pp[c * pr.sc]; }
-  // dL/dp_t = -inv/(p_t+eps);  dlogit_c = p_c*(dp_c - sum_k dp_k p_k)
-  const float gpt = (tc >= 0) ? (-inv / (pt + E2_EPS_NLL)) * pt : 0.f;
-  for (int c = 0; c < pr.c; ++c) {
-    const float pc = pp[c * pr.sc];
-    dp[c * dl.sc] = gpt * ((c == tc ? 1.f : 0.f) - pc);
-  }
+  constexpr bool WT = false;
+  const NllW wt{};
+#include "softmax_nll_bwd_body.hpp"
+}
+__global__ void softmax_nll_bwd_w_kernel(View5 pr, View5 tg, const float* __restrict__ stats,
+                                         View5 dl, float* __restrict__ loss_out, int sum_mode,
+                                         float* __restrict__ count_out, NllW wt) {
+  constexpr bool WT = true;
+#include "softmax_nll_bwd_body.hpp"
 }
 
 // ---------------------------------------------------------------------------
@@ -1203,9 +1177,8 @@ extern "C" int e2_transpose_ndhwc_to_ncdhw(e2_ctx* ctx, const float* src,
   return 0;
 }
 
-extern "C" int e2_softmax_nll_fwd(e2_ctx* ctx, const e2_tensor5* logits,
-                                  const e2_tensor5* target, const e2_tensor5* probs,
-                                  float* stats) {
+static int softmax_nll_fwd_impl(e2_ctx* ctx, const e2_tensor5* logits, const e2_tensor5* target,
+                                const e2_tensor5* probs, float* stats, const e2_nll_weights* wts) {
   E2_REQUIRE(ctx && stats, "softmax_nll_fwd: null argument");
   if (int rc = check_view(logits, "softmax_nll_fwd logits")) return rc;
   if (int rc = check_view(target, "softmax_nll_fwd target")) return rc;
@@ -1219,14 +1192,34 @@ extern "C" int e2_softmax_nll_fwd(e2_ctx* ctx, const e2_tensor5* logits,
   View5 l = mk(logits), t = mk(target), p = mk(probs);
   const long S = (long)l.d * l.h * l.w;
   dim3 grid((unsigned)((S + 255) / 256), 1, (unsigned)l.n);
-  hipLaunchKernelGGL(softmax_nll_fwd_kernel, grid, dim3(256), 0, ctx->stream, l, t, p, stats);
+  if (wts) {
+    NllW wt;
+    if (int rc = e2i_nll_weights(wts, target, "softmax_nll_fwd_w", &wt)) return rc;
+    hipLaunchKernelGGL(softmax_nll_fwd_w_kernel, grid, dim3(256), 0, ctx->stream, l, t, p, stats, wt);
+  } else {
+    hipLaunchKernelGGL(softmax_nll_fwd_kernel, grid, dim3(256), 0, ctx->stream, l, t, p, stats);
+  }
   E2_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
-extern "C" int e2_softmax_nll_bwd(e2_ctx* ctx, const e2_tensor5* probs,
-                                  const e2_tensor5* target, const float* stats,
-                                  const e2_tensor5* dlogits, float* loss_out) {
+extern "C" int e2_softmax_nll_fwd(e2_ctx* ctx, const e2_tensor5* logits,
+                                  const e2_tensor5* target, const e2_tensor5* probs,
+                                  float* stats) {
+  return softmax_nll_fwd_impl(ctx, logits, target, probs, stats, nullptr);
+}
+
+/* the weighted form (loss.py:261-347 with class_weights, example_weights, mask_class_labeled,
+ * mask_class_not_present): stats[0] += sum_up + sum_dn, stats[1] += n_tot (include/e2hip.h) */
+extern "C" int e2_softmax_nll_fwd_w(e2_ctx* ctx, const e2_tensor5* logits,
+                                    const e2_tensor5* target, const e2_tensor5* probs,
+                                    float* stats, const e2_nll_weights* wts) {
+  return softmax_nll_fwd_impl(ctx, logits, target, probs, stats, wts);
+}
+
+static int softmax_nll_bwd_impl(e2_ctx* ctx, const e2_tensor5* probs, const e2_tensor5* target,
+                                const float* stats, const e2_tensor5* dlogits, float* loss_out,
+                                const e2_nll_weights* wts) {
   E2_REQUIRE(ctx && stats, "softmax_nll_bwd: null argument");
   if (int rc = check_view(probs, "softmax_nll_bwd probs")) return rc;
   if (int rc = check_view(target, "softmax_nll_bwd target")) return rc;
@@ -1238,10 +1231,33 @@ extern "C" int e2_softmax_nll_bwd(e2_ctx* ctx, const e2_tensor5* probs,
   View5 p = mk(probs), t = mk(target), d = mk(dlogits);
   const long S = (long)p.d * p.h * p.w;
   dim3 grid((unsigned)((S + 255) / 256), 1, (unsigned)p.n);
-  hipLaunchKernelGGL(softmax_nll_bwd_kernel, grid, dim3(256), 0, ctx->stream, p, t, stats, d,
-                     loss_out, ctx->loss_sum_mode, ctx->loss_count_out);
+  if (wts) {
+    NllW wt;
+    E2_REQUIRE(target->n == probs->n, "softmax_nll_bwd_w: shape mismatch");
+    E2_REQUIRE(dlogits->ptr != probs->ptr, "softmax_nll_bwd_w: dlogits must not alias probs");
+    if (int rc = e2i_nll_weights(wts, target, "softmax_nll_bwd_w", &wt)) return rc;
+    hipLaunchKernelGGL(softmax_nll_bwd_w_kernel, grid, dim3(256), 0, ctx->stream, p, t, stats, d,
+                       loss_out, ctx->loss_sum_mode, ctx->loss_count_out, wt);
+  } else {
+    hipLaunchKernelGGL(softmax_nll_bwd_kernel, grid, dim3(256), 0, ctx->stream, p, t, stats, d,
+                       loss_out, ctx->loss_sum_mode, ctx->loss_count_out);
+  }
   E2_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+extern "C" int e2_softmax_nll_bwd(e2_ctx* ctx, const e2_tensor5* probs,
+                                  const e2_tensor5* target, const float* stats,
+                                  const e2_tensor5* dlogits, float* loss_out) {
+  return softmax_nll_bwd_impl(ctx, probs, target, stats, dlogits, loss_out, nullptr);
+}
+
+/* gradient of the weighted loss (loss.py:261-347; formulas in include/e2hip.h) */
+extern "C" int e2_softmax_nll_bwd_w(e2_ctx* ctx, const e2_tensor5* probs,
+                                    const e2_tensor5* target, const float* stats,
+                                    const e2_tensor5* dlogits, float* loss_out,
+                                    const e2_nll_weights* wts) {
+  return softmax_nll_bwd_impl(ctx, probs, target, stats, dlogits, loss_out, wts);
 }
 
 extern "C" int e2_malis_nll(e2_ctx* ctx, const e2_tensor5* probs, const float* pos,

@@ -5,9 +5,23 @@ constructor signatures (elektronn2/neuromancer/loss.py:33-93, 141-351,
 HIP execution covers the pattern every BASELINE config uses:
 ``AggregateLoss(MultinoulliNLL(Softmax(lin-Conv), target, target_is_sparse=True))``
 which reduces to  loss = sum_labelled -log(p_target + 1e-5) / (n_labelled + 1e-5)
-(the pred.size / n_class / mean factors of loss.py:342-346,1357-1363 cancel).
-Class / example weights, masks, weakness and dense targets are outside the hot path
-and raise NotImplementedError.  ``Softmax(n_indep > 1)`` (independent softmaxes over
+(the pred.size / n_class / mean factors of loss.py:342-346,1357-1363 cancel), and its
+weighted form (loss.py:172-212, 261-347): ``class_weights`` (a sequence -> a non-trainable
+parameter the kernels read in place, or an ``Input((n_class,), 'f')``), ``example_weights``
+(an Input of the target's shape without the class axis) and the lazy-labelling masks
+``mask_class_labeled`` / ``mask_class_not_present`` (Inputs ``(b, n_class)``):
+    loss = (-sum T w e log(p + eps) - sum M w e log(1 - p + eps)) / (sum T + S sum M + eps),
+    T = onehot(target) * mask_class_labeled, M = mask_class_not_present, S = positions per item.
+The weight Inputs are ordinary inputs of the loss node: extra positional arguments of
+``trainingstep(data, target, *extras)`` in the order of ``loss_node.input_nodes``, slices of the
+plan's input arena (and of an input-ring slot).  Whichever kernel the plan chose for the loss --
+the fused tail (csrc/tail.hip), the fused head (csrc/head.hip) or the generic pair
+(csrc/pointwise.hip) -- takes the weights (the ``_w`` entry points of include/e2hip.h).
+The weighted tail launch is f32 only: in bf16 mode (``set_mfma_dtype('bf16')``) a neuro3d-style net
+with a weighted loss needs the plan option ``bf16_tail`` off (the separate kernels then run; the
+choice of the path never depends on the weights, so the launch reports an error otherwise).
+Weak training, dense targets and several independent softmaxes under one MultinoulliNLL are
+outside the hot path and raise NotImplementedError.  ``Softmax(n_indep > 1)`` (independent softmaxes over
 consecutive feature groups, loss.py:82-92) exists for ``MalisNLL`` (loss.py:560-690,
 SURVEY.md 8f-4): forward and gradient on the device, the MALIS counts by the host C++
 of csrc/malis.cpp between the forward and the backward segment of the step.
@@ -90,17 +104,30 @@ class MultinoulliNLL(Node):
     def __init__(self, pred, target, target_is_sparse=False, class_weights=None,
                  example_weights=None, weakness=0, mask_class_labeled=None,
                  mask_class_not_present=None, name="nll", print_repr=True):
-        super(MultinoulliNLL, self).__init__([pred, target], name, print_repr)
+        parents = [pred, target]              # (parent order: loss.py:218-235)
+        cw_param = None
+        if class_weights is not None:
+            if isinstance(class_weights, Node):
+                parents.append(class_weights)
+            else:
+                cw_param = VariableParam(value=np.array(class_weights, dtype=floatX),
+                                         name="class_weights", dtype=floatX,
+                                         apply_train=False)
+        for extra in (example_weights, mask_class_labeled, mask_class_not_present):
+            if extra is not None:
+                if not isinstance(extra, Node):
+                    raise ValueError("example_weights and the class masks must be Nodes")
+                parents.append(extra)
+        super(MultinoulliNLL, self).__init__(parents, name, print_repr)
         if not isinstance(pred, Softmax):
             raise ValueError("The prob input to a MultinoulliNLL-node must be "
                              "a Softmax-Node.")
         if pred.n_indep != 1:
             raise NotImplementedError("MultinoulliNLL over n_indep > 1 is outside the "
                                       "HIP hot path")
-        if (class_weights is not None or example_weights is not None or weakness or
-                mask_class_labeled is not None or mask_class_not_present is not None):
-            raise NotImplementedError("class/example weights, masks and weak training "
-                                      "are outside the HIP hot path")
+        if weakness:
+            raise NotImplementedError("weak training (weakness != 0) is outside the HIP "
+                                      "hot path")
         if not target_is_sparse:
             raise NotImplementedError("dense (one-hot) targets are outside the HIP hot path")
         self.target = target
@@ -109,9 +136,66 @@ class MultinoulliNLL(Node):
         self.n_class = pred.n_class
         self.n_indep = pred.n_indep
         self.target_is_sparse = target_is_sparse
-        self.class_weights = None
-        self.example_weights = None
+        k = self.n_class
+        if cw_param is not None:
+            if cw_param.shape != (k,):
+                raise ValueError("class_weights: %i values given, the prediction has %i "
+                                 "classes" % (int(np.prod(cw_param.shape)), k))
+            self.params['class_weights'] = cw_param
+            class_weights = cw_param
+        elif class_weights is not None:
+            if tuple(class_weights.shape.tags) != ('f',) or \
+                    tuple(class_weights.shape.shape) != (k,):
+                raise ValueError("class_weights node: an Input((%i,), 'f') is needed, got %s"
+                                 % (k, class_weights.shape))
+        for what, m in (('mask_class_labeled', mask_class_labeled),
+                        ('mask_class_not_present', mask_class_not_present)):
+            if m is not None and (tuple(m.shape.tags) != ('b', 'f') or m.shape['f'] != k
+                                  or m.shape['b'] != pred.shape['b']):
+                raise ValueError("%s: an Input((%r, %i), 'b,f') is needed, got %s"
+                                 % (what, pred.shape['b'], k, m.shape))
+        if example_weights is not None:
+            tags = tuple(t for t in pred.shape.tags if t != 'f')
+            shape = tuple(s for s, t in zip(pred.shape.shape, pred.shape.tags) if t != 'f')
+            if tuple(example_weights.shape.tags) != tags or \
+                    tuple(example_weights.shape.shape) != shape:
+                raise ValueError("example_weights: an Input(%s, '%s') is needed (the target's "
+                                 "shape without the class axis), got %s"
+                                 % (shape, ",".join(tags), example_weights.shape))
+        self.class_weights = class_weights
+        self.example_weights = example_weights
         self.weakness = 0
+        self.mask_class_labeled = mask_class_labeled
+        self.mask_class_not_present = mask_class_not_present
+
+    @property
+    def weighted(self):
+        return any(v is not None for v in (self.class_weights, self.example_weights,
+                                           self.mask_class_labeled,
+                                           self.mask_class_not_present))
+
+    def _weights(self, plan):
+        """the e2_nll_weights descriptor of this plan (None: the unweighted entry points).  It
+        names device buffers -- the class-weight parameter's slice of the parameter arena, the
+        weight Inputs' slices of the input arena -- that the kernels read when they run: new
+        values need no new capture."""
+        if not self.weighted:
+            return None
+        w = plan.scratch.get((self, 'weights'))
+        if w is None:
+            from .. import backend
+            cw = self.class_weights
+            if isinstance(cw, VariableParam):
+                cw = plan.param(cw).reshape(-1)
+            elif cw is not None:
+                cw = plan.out[cw].reshape(-1)
+            dev = lambda node: None if node is None else plan.out[node]
+            lab, npr = dev(self.mask_class_labeled), dev(self.mask_class_not_present)
+            w = backend.nll_weights(class_w=cw, example_w=dev(self.example_weights),
+                                    labelled=None if lab is None else lab.reshape(lab.shape[0], -1),
+                                    not_present=None if npr is None else npr.reshape(npr.shape[0], -1))
+            plan.scratch[self, 'weights'] = w
+        return w
 
     def _calc_shape(self):
         self.shape = self.parent[0].shape.updateshape(self.axis, 1)
@@ -162,16 +246,18 @@ class MultinoulliNLL(Node):
                     plan.out[par], plan.scratch[tail, 'wp_f'], plan.scratch.get((tail, 'wp_d')),
                     plan.param(tail.b), plan.param(head.w).reshape(head.n_f, -1),
                     plan.param(head.b), plan.out[self.target], plan.out[self.pred],
-                    plan.scratch[tail, 'dy'], dx, stats, plan.scratch[tail, 'tail_ws'], **kw)
+                    plan.scratch[tail, 'dy'], dx, stats, plan.scratch[tail, 'tail_ws'],
+                    weights=self._weights(plan), **kw)
             return
         plan.zero_early(stats)
         head = self.pred._head(plan)
         if head is not None:
             plan.ctx.head_fwd(plan.out[head.parent], plan.param(head.w), plan.param(head.b),
-                              plan.out[self.target], plan.out[self.pred], stats)
+                              plan.out[self.target], plan.out[self.pred], stats,
+                              weights=self._weights(plan))
             return
         plan.ctx.softmax_nll_fwd(plan.out[self.pred.parent], plan.out[self.target],
-                                 plan.out[self.pred], stats)
+                                 plan.out[self.pred], stats, weights=self._weights(plan))
 
     def _plan_bwd(self, plan):
         with plan.loss_grad_mode():
@@ -196,7 +282,8 @@ class MultinoulliNLL(Node):
             plan.ctx.head_bwd(plan.out[head.parent], plan.param(head.w), plan.out[self.pred],
                               plan.out[self.target], plan.scratch[self.pred, 'stats'], dst,
                               not first, plan.pgrad(head.w), plan.pgrad(head.b),
-                              plan.scratch[self, 'loss'], ws=plan.scratch[self, 'head_ws'])
+                              plan.scratch[self, 'loss'], ws=plan.scratch[self, 'head_ws'],
+                              weights=self._weights(plan))
             return
         logits = self.pred.parent
         dst, first = plan.grad_slot(logits)
@@ -204,10 +291,10 @@ class MultinoulliNLL(Node):
             raise NotImplementedError("logits consumed by several nodes")
         plan.ctx.softmax_nll_bwd(plan.out[self.pred], plan.out[self.target],
                                  plan.scratch[self.pred, 'stats'], dst,
-                                 plan.scratch[self, 'loss'])
+                                 plan.scratch[self, 'loss'], weights=self._weights(plan))
 
     def loss_value(self, plan):
-        """device scalar: loss_sum / (n_labelled + EPS)."""
+        """device scalar: loss_sum / (n_labelled + EPS)  (weighted: (sum_up + sum_dn) / (n_tot + EPS))."""
         s = plan.scratch[self.pred, 'stats']
         return s[0] / (s[1] + EPS)
 

@@ -133,6 +133,13 @@ class Plan(object):
         if len(sh) == 5:
             return sh
         tags = tuple(node.shape.tags)
+        # the two source shapes of the weighted MultinoulliNLL (loss.py:172-212): class weights
+        # ('f') and example weights ('b' + spatial axes, no 'f')
+        if tags == ('f',):
+            return (1, sh[0], 1, 1, 1)
+        if 2 <= len(sh) <= 4 and tags[0] == 'b' and 'f' not in tags and \
+                all(t in ('z', 'x', 'y') for t in tags[1:]):
+            return sh[:1] + (1,) * (5 - len(sh)) + sh[1:]
         if len(sh) < 2 or len(sh) > 5 or tags[0] != 'b' or tags[1] != 'f':
             raise NotImplementedError("axis order %s: the device layout is (b, f, spatial...)"
                                       % (",".join(tags),))
@@ -1111,7 +1118,7 @@ class Plan(object):
                 elif int(s) != int(g):
                     raise TypeError("input '%s': shape %s given, %s required"
                                     % (node.name, tuple(a.shape), tuple(decl)))
-            if decl[node.shape.tag2index('b')] is not None:
+            if node.shape.hastag('b') and decl[node.shape.tag2index('b')] is not None:
                 batch = decl[node.shape.tag2index('b')] if batch is None else batch
         if batch is None:
             batch = 1

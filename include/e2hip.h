@@ -438,6 +438,50 @@ int e2_softmax_nll_bwd(e2_ctx*, const e2_tensor5* probs,
                        const e2_tensor5* target, const float* stats,
                        const e2_tensor5* dlogits, float* loss_out);
 
+/* ---- weighted MultinoulliNLL: class / example weights and the lazy-labelling masks
+ *      (loss.py:172-212 arguments, loss.py:261-347 computation; n_indep = 1, sparse targets,
+ *      weakness = 0).  With t = target class id (< 0: unlabelled), w = class_w, e = example_w,
+ *      L = labelled (mask_class_labeled), M = not_present (mask_class_not_present), S = positions
+ *      per batch item:
+ *        T[b,c,v] = [t[b,v] == c] * L[b,c]
+ *        stats[0] = - sum T w e log(p + 1e-5)  -  sum_{ALL voxels} M w e log((1 - p) + 1e-5)
+ *        stats[1] = sum T + S * sum M           (a count: the weights do not enter it)
+ *        loss     = stats[0] / (stats[1] + 1e-5)
+ *        dloss/dp = (-T w e / (p + 1e-5) + M w e / ((1 - p) + 1e-5)) / (stats[1] + 1e-5)
+ *      1 - p_c is formed as the sum of the OTHER classes' terms, never by subtraction (f32
+ *      loses every digit of it where a not-present class saturates).  NULL members take their
+ *      default; all members NULL, or a NULL descriptor, is the unweighted loss.  The arrays are
+ *      device memory, read at launch time (a captured graph follows their contents).  The _w
+ *      entry points take the arguments of their unweighted siblings and honour
+ *      e2_set_loss_grad_mode the same way (count_out = stats[1]).  e2_tail_fwd_bwd_w is f32
+ *      only: in bf16 mode (e2_set_mfma_dtype) it is an error -- use the head / conv entry points. ----------------------- */
+typedef struct e2_nll_weights {
+  const float*      class_w;      /* [ncls]                                  NULL: 1 */
+  const e2_tensor5* example_w;    /* (n, 1, d, h, w), spatial = the target's NULL: 1 */
+  const float*      labelled;     /* [n][ncls]  mask_class_labeled           NULL: 1 */
+  const float*      not_present;  /* [n][ncls]  mask_class_not_present       NULL: 0 */
+} e2_nll_weights;
+int e2_softmax_nll_fwd_w(e2_ctx*, const e2_tensor5* logits, const e2_tensor5* target,
+                         const e2_tensor5* probs, float* stats, const e2_nll_weights* wts);
+/* (dlogits must not alias probs: the weighted backward keeps partial sums in dlogits while it
+ * still reads the probabilities -- the unweighted one has no such restriction) */
+int e2_softmax_nll_bwd_w(e2_ctx*, const e2_tensor5* probs, const e2_tensor5* target,
+                         const float* stats, const e2_tensor5* dlogits, float* loss_out,
+                         const e2_nll_weights* wts);
+int e2_head_fwd_w(e2_ctx*, const e2_tensor5* x, const float* w, const float* bias, int ncls,
+                  const e2_tensor5* target, const e2_tensor5* probs, float* stats,
+                  const e2_nll_weights* wts);
+int e2_head_bwd_w(e2_ctx*, const e2_tensor5* x, const float* w, const e2_tensor5* probs,
+                  const e2_tensor5* target, const float* stats, const e2_tensor5* dx,
+                  int accumulate_dx, float* dw, float* dbias, float* loss_out, void* ws,
+                  size_t ws_bytes, const e2_nll_weights* wts);
+int e2_tail_fwd_bwd_w(e2_ctx*, const e2_tensor5* x, const float* wp_fwd, const float* wp_dgrad,
+                      const float* bias1, int c2, const float* w_head, const float* b_head,
+                      int ncls, const e2_tensor5* target, const e2_tensor5* probs,
+                      const e2_tensor5* dpre, const e2_tensor5* dx, int gm_mode,
+                      const e2_tensor5* gm_src, const float* gm_bias, float* stats, void* ws,
+                      size_t ws_bytes, int* n_slots, const e2_nll_weights* wts);
+
 /* MALIS NLL (neuromancer/loss.py:560-690 MalisNLL; malis/malisop.py:19-123): probs is
  * (1, 2E, d, h, w) -- E independent 2-class softmaxes, channel 2e = "disconnected",
  * 2e+1 = affinity of edge e; pos / neg: dense (E, d, h, w) float MALIS counts (from
