@@ -195,6 +195,9 @@ def _load():
         "e2_batchnorm_act_fwd": (C.c_int, [vp, P5, fp, fp, fp, fp, i, i, i, P5, fp]),
         "e2_batchnorm_act_bwd": (C.c_int, [vp, P5, P5, fp, fp, fp, i, i, P5, fp, fp]),
         "e2_get_mfma_dtype": (C.c_int, [vp]),
+        "e2_dropout_fwd": (C.c_int, [vp, P5, P5, i, fp, vp, C.c_uint32]),
+        "e2_dropout_bwd": (C.c_int, [vp, P5, P5, i, fp, vp, C.c_uint32]),
+        "e2_dropout_tick": (C.c_int, [vp, vp]),
         "e2_adam_step": (C.c_int, [vp, fp, fp, fp, fp, sz, vp, fp, i, fp]),
         "e2_sgd_step": (C.c_int, [vp, fp, fp, fp, sz, vp, fp, i, fp]),
         "e2_set_loss_grad_mode": (C.c_int, [vp, i, fp]),
@@ -666,6 +669,32 @@ class Context:
             raise TypeError("fill needs a contiguous tensor")
         _chk(_lib.e2_fill(self.h, C.c_void_p(t.data_ptr()), t.numel(), float(value)),
              "e2_fill")
+
+    # ---- dropout (e2hip.h: the gate contract) ------------------------------------------
+    @staticmethod
+    def _drop_state(state):
+        if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.int32
+                and state.numel() >= 4 and state.is_contiguous() and state.data_ptr() % 16 == 0):
+            raise TypeError("dropout state: four int32 words in device memory, 16-byte aligned")
+        return C.c_void_p(state.data_ptr())
+
+    def dropout_fwd(self, x, out, rate, state, stream, feature_mode=False):
+        """out = gate(x) (``out`` may be ``x``); ``rate``: a one-element float32 device tensor,
+        ``state``: int32[4] device tensor (seed lo, seed hi, counter, -) -- both read when the
+        kernel RUNS"""
+        _chk(_lib.e2_dropout_fwd(self.h, C.byref(t5(x)), C.byref(t5(out)), int(bool(feature_mode)),
+                                 _fp(rate), self._drop_state(state), int(stream) & 0xffffffff),
+             "e2_dropout_fwd")
+
+    def dropout_bwd(self, dout, dx, rate, state, stream, feature_mode=False):
+        """dx = gate(dout), the gate of dropout_fwd for the same state and stream"""
+        _chk(_lib.e2_dropout_bwd(self.h, C.byref(t5(dout)), C.byref(t5(dx)), int(bool(feature_mode)),
+                                 _fp(rate), self._drop_state(state), int(stream) & 0xffffffff),
+             "e2_dropout_bwd")
+
+    def dropout_tick(self, state):
+        """state's counter += 1: the launch in front of a step's dropout launches"""
+        _chk(_lib.e2_dropout_tick(self.h, self._drop_state(state)), "e2_dropout_tick")
 
     # ---- loss / optimiser ----------------------------------------------------------
     def softmax_nll_fwd(self, logits, target, probs, stats, weights=None):

@@ -146,6 +146,10 @@ def prepare(plan):
         from .neural import Conv
         if type(par) is not Conv or not hasattr(par, '_k3') or par.parent is None:
             continue
+        if par.dropout_rate is not None:
+            # (its kernels would write the image from the output BEFORE dropout gates it: the
+            # consumer converts the gated output for itself, as for any layer without a producer)
+            continue
         if par._fused_first(plan):
             if par.n_f > 32:              # (the matrix-core form of the fused first layer only)
                 continue

@@ -5,7 +5,7 @@ Kept from the reference: ``designate_nodes`` (model.py:95-227) including the
 fov fix-up for UpConv nets (141-152), ``trainingstep(*batch, optimiser=)`` ->
 ``(loss, t_seconds, None)`` (548-600), ``loss / predict / predict_ext /
 gradients``, the ``lr / mom / wd`` properties that act on optimiser globals
-(282-322), ``set_opt_meta_params``, ``get/set_param_values``.
+(282-322), ``set_opt_meta_params``, ``get/set_param_values``, ``dropout_rates`` (365-396).
 
 Replaced: ``T.grad`` + Theano update lists become a training ``Plan``
 (plan.py) over hand-written HIP kernels.  All trainable parameters live in one
@@ -110,6 +110,10 @@ class Model(GraphManager):
         self._slots = None          # id(param) -> (offset, size, shape)
         self._ctx = None
         self._dp_group = None
+        # dropout: the generator state shared by every plan of the model (seed, counter); on the
+        # host until a plan needs it on the device
+        self._drop_host = None      # (seed, counter the next plan run uses)
+        self._drop_dev = None       # int32[4] on the device: seed lo, seed hi, counter, -
 
     # ------------------------------------------------------------------ designate
     def designate_nodes(self, input_node='input', target_node=None, loss_node=None,
@@ -248,6 +252,13 @@ class Model(GraphManager):
         self._dp_force = bool(exchange_at_world_1)
         self.broadcast_params()
 
+    def dp_rank(self):
+        """this process's rank in the data-parallel group (0 without one)"""
+        if self._dp_group is None:
+            return 0
+        import torch.distributed as dist
+        return dist.get_rank(self._dp_group)
+
     def dp_world(self):
         """ranks that exchange gradients (1: no exchange).  A one-rank group counts as 2
         when the exchange was forced (enable_data_parallel(exchange_at_world_1=True))."""
@@ -287,6 +298,81 @@ class Model(GraphManager):
         return BucketedMean(self.G, self._dp_group,
                             count=count if getattr(self, '_dp_weighted', False) else None,
                             spare=True, force=getattr(self, '_dp_force', False))
+
+    # ------------------------------------------------------------------ dropout
+    def dropout_nodes(self):
+        """the nodes that own a ``dropout_rate`` parameter, in node order (a node built with
+        rate 0 has none, neural.py:246-249)"""
+        return [n for n in self.nodes.values() if n.params.get('dropout_rate', None) is not None]
+
+    @property
+    def dropout_rates(self):
+        """model.py:365-376: the rates of the dropout nodes in node order (empty for a net
+        without dropout).  Dropout acts in EVERY function of the model while a rate is non-zero;
+        the reference's trainer sets the rates to 0 around validation and previews
+        (training/trainer.py:378-403)."""
+        return np.array([n.params['dropout_rate'].get_value() for n in self.dropout_nodes()])
+
+    @dropout_rates.setter
+    def dropout_rates(self, rates):
+        """model.py:378-396: a number -> every dropout node; a tuple / list / array -> the nodes in
+        their order.  The value goes to the parameter's slot in device memory, which the gate
+        kernels read when they run: captured graphs stay valid."""
+        from .neural import check_dropout_rate
+        nodes = self.dropout_nodes()
+        seq = isinstance(rates, (tuple, list, np.ndarray)) and np.ndim(rates) > 0
+        if seq and len(rates) < len(nodes):
+            raise ValueError("%d dropout rates given, the model has %d dropout nodes"
+                             % (len(rates), len(nodes)))
+        vals = [check_dropout_rate(np.ravel(rates[i])[0] if seq else rates)
+                for i in range(len(nodes))]
+        for n, v in zip(nodes, vals):
+            n.params['dropout_rate'].set_value(np.full((1,), v, dtype=graphutils.floatX))
+
+    def set_dropout_seed(self, seed, counter=0):
+        """Seed the gate generator: the next plan run of this model (training, loss, prediction
+        -- they share the state) draws the gates of ``(seed, counter)``, the one after it of
+        ``counter + 1``, ...  (include/e2hip.h, the gate contract).  Without a call the seed is
+        ``int(time.time())``, as the reference seeds its stream.  Neither seed nor
+        counter is part of a checkpoint (the reference reseeds on every build); the rates are."""
+        self._drop_host = (int(seed) & 0xffffffffffffffff, int(counter) & 0xffffffff)
+        if self._drop_dev is not None:
+            self._drop_upload()
+
+    def _drop_upload(self):
+        import torch
+        seed, counter = self._drop_host
+        # (the tick launch in front of a run's gate launches adds 1: store the value before it)
+        words = np.array([seed & 0xffffffff, seed >> 32, (counter - 1) & 0xffffffff, 0], dtype=np.uint32)
+        dev = self._ctx.device
+        torch.cuda.synchronize(dev)            # (plans run on streams of their own)
+        if self._drop_dev is None:
+            self._drop_dev = torch.zeros(4, dtype=torch.int32, device=dev)
+        self._drop_dev.copy_(torch.from_numpy(words.view(np.int32)))
+        torch.cuda.synchronize(dev)
+
+    def dropout_state_dev(self):
+        """the device-side generator state the gate launches read (made on first use, never
+        during a capture: Plan.build asks for it)"""
+        if self._drop_dev is None:
+            if self._drop_host is None:
+                import time
+                self._drop_host = (int(time.time()), 0)
+            self._drop_upload()
+        return self._drop_dev
+
+    def dropout_state(self):
+        """``dict(seed=, counter=)``: ``counter`` is the value the NEXT plan run will use,
+        whichever plan of the model it is (host read-back: waits for the device)."""
+        if self._drop_dev is None:
+            if self._drop_host is None:
+                import time
+                self._drop_host = (int(time.time()), 0)
+            return dict(seed=self._drop_host[0], counter=self._drop_host[1])
+        import torch
+        torch.cuda.synchronize(self._ctx.device)
+        w = self._drop_dev.cpu().numpy().view(np.uint32)
+        return dict(seed=int(w[0]) | (int(w[1]) << 32), counter=(int(w[2]) + 1) & 0xffffffff)
 
     # ------------------------------------------------------------------ functions
     def save(self, file_name):

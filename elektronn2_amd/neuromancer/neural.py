@@ -14,8 +14,16 @@ bookkeeping (elektronn2/neuromancer/neural.py), executing through libe2hip.so.
 kernels with a unit z axis; batch normalisation ('train' / 'predict', neural.py:681-711)
 has its own kernel (csrc/dense_bn.hip).
 
+Dropout (``dropout_rate=`` of Conv / UpConv / Perceptron, neural.py:246-249,391-397,714-720,
+1064-1070) is the last thing a node does to its output: one launch in place on the node's
+output, and one on its output gradient in front of the node's backward launches, with gates
+made on the device by a counter-based generator (csrc/dropout.hip; the gate contract is in
+include/e2hip.h).  A node with dropout keeps off the routes that never materialise those two
+tensors (fused head, tail, activation backward inside a consumer's launch, gradient slabs,
+bf16 operand images written by the producer); a node without it is untouched.
+
 Outside the hot path and therefore rejected with NotImplementedError here:
-dropout, gradnet, batch_normalisation='fadeout', activations other than 'relu' / 'lin',
+gradnet, batch_normalisation='fadeout', activations other than 'relu' / 'lin',
 conv modes other than 'valid', 1-D convolutions.
 """
 from __future__ import annotations
@@ -38,8 +46,44 @@ __all__ = ['Conv', 'UpConv', 'Pool', 'Crop', 'AutoMerge', 'UpConvMerge', 'Neural
 _HIP_ACTS = ('relu', 'lin')
 
 
+def check_dropout_rate(rate):
+    """a dropout rate is a probability below 1 (at 1 nothing would be kept and the scale
+    1 / (1 - rate) has no value)"""
+    r = float(rate)
+    if not (0.0 <= r < 1.0):
+        raise ValueError("dropout rate %r is outside [0, 1)" % (rate,))
+    return r
+
+
 class NeuralLayer(Node):
     """Parameter plumbing shared by Conv / UpConv (neural.py:37-256)."""
+
+    # dropout gate per output element (Conv, UpConv: neural.py:714-720, 1064-1070); the
+    # Perceptron draws one per output feature (neural.py:391-397)
+    _drop_per_feature = False
+
+    def _drop_fwd(self, plan):
+        """dropout, the last thing a node does to its output (neural.py:712-722): in place on
+        the output, whatever view that is (a Concat slice, MFP fragments on the batch axis).
+        Called by the plan behind _plan_fwd of a node that owns a dropout_rate."""
+        out = plan.out.get(self)
+        if out is None:
+            raise RuntimeError("dropout node %s: its output is not materialised" % self.name)
+        plan.ctx.dropout_fwd(out, out, plan.param(self.dropout_rate), plan.model.dropout_state_dev(),
+                             plan.dropout_stream(self), feature_mode=self._drop_per_feature)
+
+    def _drop_bwd(self, plan):
+        """the same gate on the output gradient, in front of the node's backward launches
+        (T.grad of the product, neural.py:714-720).  What the activation backward reads next to
+        it stays valid: routes that read the PRE-activation do not see the gate at all; routes
+        that read the activated output (fused epilogue, UpConv) see kept elements with their sign
+        unchanged (the scale is positive, -0 stays -0) and dropped ones as +0, where the gated
+        gradient is 0 whatever slope relu'(0) = 0.5 assigns."""
+        g = plan.grad.get(self)
+        if g is None:
+            raise RuntimeError("dropout node %s: its output gradient is not materialised" % self.name)
+        plan.ctx.dropout_bwd(g, g, plan.param(self.dropout_rate), plan.model.dropout_state_dev(),
+                             plan.dropout_stream(self), feature_mode=self._drop_per_feature)
 
     def _register_param(self, param, shape, name, init_kwargs=None,
                         apply_train=False, apply_reg=False):
@@ -87,7 +131,7 @@ class NeuralLayer(Node):
 
     def _setup_params(self, w_sh, w, b, gamma, mean, std, dropout_rate,
                       pool_shape=None, gradnet_rate=None):
-        """neural.py:146-256 (BN / dropout / gradnet branches are out of scope)."""
+        """neural.py:146-256 (the gradnet branch is out of scope)."""
         from .. import config
         self.w = None
         w_init = dict(scale='glorot', mode='ortho' if config.use_ortho_init else 'normal',
@@ -138,9 +182,13 @@ class NeuralLayer(Node):
                                       "outside the HIP hot path")
         elif bn is not False and bn is not None:
             raise ValueError("Unknown value %s for batchnormalisation" % (bn,))
+        # neural.py:246-249: a non-trainable (1,) parameter, created only for a non-zero rate --
+        # a node built with 0 has none and can never be switched on later
         self.dropout_rate = None
         if dropout_rate:
-            raise NotImplementedError("dropout is outside the HIP hot path")
+            check_dropout_rate(dropout_rate)
+            self._register_param(np.full((1,), float(dropout_rate), dtype=floatX), (1,),
+                                 'dropout_rate', apply_train=False, apply_reg=False)
         self.gradnet_rate = None
         if gradnet_rate:
             raise NotImplementedError("gradnet is outside the HIP hot path")
@@ -326,7 +374,10 @@ class Conv(NeuralLayer):
 
     def _fused_first(self, plan):
         """Cin = 1 first layer with a supported kernel/pool: fused conv+pool+bias+act
-        kernels that never materialise the conv output (csrc/conv_first.hip)."""
+        kernels that never materialise the conv output (csrc/conv_first.hip).  (A dropout
+        node keeps this route: the pair materialises the node's output and reads its output
+        gradient, the two tensors the gate is applied to; the backward kernel recomputes the
+        pre-activation from x and never reads the gated output.)"""
         return (not self._bn() and self.parent.is_source and self.parent.shape['f'] == 1 and
                 plan.ctx.conv1_supported(1, self._k3, self._p3) and
                 not plan.needs_grad(self.parent) and not self._mfp_pool())
@@ -343,6 +394,7 @@ class Conv(NeuralLayer):
             sm = None
             kids = list(self.children.values())
             if (type(self) is Conv and not self._bn() and tuple(self._k3) == (1, 1, 1)
+                    and self.dropout_rate is None          # (the logits must exist to be gated)
                     and all(p == 1 for p in self._p3) and self.activation_func == 'lin'
                     and len(kids) == 1 and type(kids[0]).__name__ == 'Softmax'
                     and kids[0].n_indep == 1
@@ -366,6 +418,7 @@ class Conv(NeuralLayer):
             par = self.parent
             if (plan.opt['fuse_tail'] and plan.training
                     and type(self) is Conv and not self._bn() and not self.mfp
+                    and self.dropout_rate is None       # (neither activations nor their gradient exist)
                     and tuple(self._k3) == (1, 1, 1) and all(p == 1 for p in self._p3)
                     and self.activation_func == 'relu' and len(kids) == 1
                     and type(kids[0]) is Conv and not isinstance(par, (list, tuple))
@@ -399,6 +452,7 @@ class Conv(NeuralLayer):
             # of its two gradient GEMMs (bf16_ahead.py) -- the tail hands it the plain gradient
             return None
         if not (plan.opt['tail_gm'] and type(par) is Conv and not par._bn()
+                and par.dropout_rate is None     # (its output gradient has to exist to be gated)
                 and all(p == 1 for p in par._p3) and par.activation_func in ('relu', 'lin')
                 and (par, 'dy') in plan.scratch and not par._fused_first(plan)
                 and par._fused_head(plan) is None and par._tail(plan) is None
@@ -486,7 +540,8 @@ class Conv(NeuralLayer):
             plan.scratch[self, 'y_parts'] = yp
             plan.scratch[self, 'y'] = yp[0]
         plan.alloc_out(self)
-        if plan.training and self in plan.grad and self._parts_ok(plan):
+        # (a dropout node gates its output gradient in place: one buffer, no slabs)
+        if plan.training and self in plan.grad and self._parts_ok(plan) and self.dropout_rate is None:
             gsh = tuple(plan.grad[self].shape)
             if self._n_parts(gsh) > 1:         # the output gradient, as slabs for partial sums
                 gp = plan.empty((self._n_parts(gsh),) + gsh)
@@ -852,6 +907,7 @@ class Conv(NeuralLayer):
         from this node alone"""
         par = self.parent
         if not (plan.fuse_actbwd and type(par) is Conv and type(self) is Conv
+                and par.dropout_rate is None     # (its output gradient has to exist to be gated)
                 and not par._bn() and all(p == 1 for p in par._p3)
                 and par.activation_func in ('relu', 'lin')
                 and (par, 'dy_pad') in plan.scratch
@@ -868,6 +924,8 @@ class Perceptron(NeuralLayer):
     """Perceptron layer (neural.py:258-410): ``act((gamma / std) * dot(x, w) + b - ...)``;
     ``w`` has the reference's (n_in, n_f) shape; ``flatten=True`` joins every non-batch axis
     of the parent (C order).  Device side: csrc/dense_bn.hip."""
+
+    _drop_per_feature = True      # size=(n_f,), broadcast over the batch (neural.py:391-397)
 
     def __init__(self, parent, n_f, activation_func='relu',
                  flatten=False, batch_normalisation=False, dropout_rate=0,

@@ -81,6 +81,10 @@ class Plan(object):
                           if self.training else set())
         self._ng_cache = {}
         self._dp_cut_cache = False
+        # nodes that own a dropout_rate parameter (neural.py:246-249): only a plan that has one
+        # issues the tick and the gate launches
+        self._drop_nodes = [n for n in self.nodes if getattr(n, 'dropout_rate', None) is not None]
+        self._drop_ids = set(id(n) for n in self._drop_nodes)
 
     # ---- allocation helpers ---------------------------------------------------
     SLACK = 32       # floats of ZEROED slack behind every tensor of the plan (e2_set_input_slack)
@@ -180,6 +184,14 @@ class Plan(object):
 
     def param(self, p):
         return self.model.device_param(p)
+
+    def dropout_stream(self, node):
+        """the ``stream`` word of the node's gate launches: its ordinal among the MODEL's dropout
+        nodes (fixed at plan build; the same in every plan of the model), plus the rank's offset
+        in a data-parallel group (parallel.dropout_stream; read when the launches are issued --
+        the step is issued and captured again when data parallelism is switched on, _dp_key)"""
+        from .. import parallel
+        return parallel.dropout_stream(self._drop_ordinal[node], self.model.dp_rank())
 
     # ---- bf16 mode: the kernel with bf16 operands in memory (csrc/conv_bf16.hip) ----------
     def bf16_cands(self, k_channels):
@@ -464,6 +476,10 @@ class Plan(object):
         self._pack_rows_done = False
         self._img_stride = {}        # id(packed image) -> floats per row it is packed with (absent: formula)
         self.model.ensure_arena(self.ctx)
+        order = dict((id(n), i) for i, n in enumerate(self.model.dropout_nodes()))
+        self._drop_ordinal = dict((n, order[id(n)]) for n in self._drop_nodes)
+        if self._drop_nodes:
+            self.model.dropout_state_dev()       # (allocates: before any capture)
         with torch.cuda.stream(self.stream):
             # the static input buffers of all Input nodes are slices of ONE allocation (each
             # 16-byte aligned): a producer that stages a batch in the same layout fills them
@@ -659,8 +675,11 @@ class Plan(object):
                     # (which reads neither) instead of behind it
                     self.ensure_wb()
             self.on_side(packs, always=True)
+        drop = self._drop_ids
         for n in self.nodes:
             n._plan_fwd(self)
+            if id(n) in drop:
+                n._drop_fwd(self)
         self.join_side()
 
     def ensure_wb(self):
@@ -688,7 +707,10 @@ class Plan(object):
             if not self._upd_zeroes_g():       # (else: the optimiser kernel left it zero)
                 self.zero_early(self.model.G)
             self._grad_written = set()
+        drop = self._drop_ids
         for n in nodes:
+            if id(n) in drop:
+                n._drop_bwd(self)
             n._plan_bwd(self)
         self.join_side()
 
@@ -750,10 +772,12 @@ class Plan(object):
         (a flag flipped after capture made the host exchange scale by the count while
         the captured optimiser still divided by it)."""
         m = self.model
+        # (a plan with dropout nodes has the rank in its launch arguments: dropout_stream)
+        rank = (m.dp_rank(),) if self._drop_nodes else ()
         if not self.training:
-            return (1,)
+            return (1,) + rank
         return (m.dp_world(), bool(getattr(m, '_dp_weighted', False)), bool(getattr(m, '_dp_force', False)),
-                id(getattr(m, '_dp_group', None)))
+                id(getattr(m, '_dp_group', None))) + rank
 
     def _dp_scale_now(self):
         """how the data-parallel step normalises: None = the exchange object scales with
@@ -946,8 +970,14 @@ class Plan(object):
                 self.model._img_owner = self if self._upd is not None else None
 
     def _emit_seg(self, i, emit, zero_jobs):
-        """the launches of segment i: (the step's prologue) + (batched zero fills) + the segment"""
+        """the launches of segment i: (the step's prologue) + (the dropout tick) + (batched zero
+        fills) + the segment"""
         ctx = self.ctx
+        if i == 0 and self._drop_nodes:
+            # once per step, in its first segment and in front of every gate launch, which read
+            # the counter it leaves: each replay of the captured step (each of the k steps of a
+            # run_steps graph) draws new gates, forward and backward of one step the same
+            ctx.dropout_tick(self.model.dropout_state_dev())
         if i == 0 and (self._ring is not None or self._hist is not None):
             # ONE launch: this step's batch out of the ring, the previous step's loss into the history
             ctx.step_prologue(self._step_state, ring=self._ring, dst=self.input_arena,

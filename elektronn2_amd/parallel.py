@@ -35,6 +35,17 @@ def local_device(backend=None, local_rank=None, device_count=None):
                        % (idx, device_count))
 
 
+def dropout_stream(ordinal, rank=0):
+    """The ``stream`` word of a dropout node's launches (include/e2hip.h, the gate contract):
+    the node's ordinal among the model's dropout nodes, plus ``rank << 16`` so that the replicas
+    of a data-parallel group draw independent gates from one seed (the reference is
+    single-process and seeds with the wall clock)."""
+    ordinal, rank = int(ordinal), int(rank)
+    if not (0 <= ordinal < (1 << 16) and 0 <= rank < (1 << 16)):
+        raise ValueError("dropout_stream: ordinal and rank must be below 65536")
+    return (rank << 16) | ordinal
+
+
 def check_distinct_devices(ranks, backend):
     """``ranks``: one dict per rank with 'rank', 'host', 'pci' (and 'uuid').  Under RCCL two
     ranks on the same GPU of the same host are a mis-bound launch: raise, naming them.  (A

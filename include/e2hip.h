@@ -766,6 +766,44 @@ int e2_batchnorm_act_bwd(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* x,
                          const float* gamma, const float* bias, const float* save, int train,
                          int act, const e2_tensor5* dx, float* dgamma, float* dbias);
 
+/* ---- dropout (neural.py:246-249 the rate parameter; 391-397 Perceptron: one gate per output
+ *      feature; 714-720 Conv and 1064-1070 UpConv: one gate per output element; the last thing a
+ *      node does to its output) ---------------------------------------------------
+ * The reference draws Bernoulli(1 - rate) gates from Theano's MRG stream, seeded with the wall
+ * clock, multiplies the activated output by gate / (1 - rate) and lets T.grad send the output
+ * gradient through the same product.  Here the gate is a pure function of (seed, counter, stream,
+ * element index) -- Philox4x32-10 (Salmon et al. 2011: multipliers 0xD2511F53 / 0xCD9E8D57, key
+ * increments 0x9E3779B9 / 0xBB67AE85) -- so that the backward pass REGENERATES it; no mask is
+ * ever stored.  The contract (tests restate it in NumPy):
+ *
+ *   j     = gate index of the element (64-bit): its row-major index in the LOGICAL dense shape
+ *           (n, c, d, h, w) of the view in element mode; its feature index c in feature mode
+ *   word  = philox4x32_10(ctr = (lo32(j >> 2), hi32(j >> 2), stream, counter),
+ *                         key = (lo32(seed), hi32(seed)))[j & 3]
+ *   T     = rate >= 1 ? 0xffffffff : (uint32)(rate * 4294967296.0f)        (exact: a power of two)
+ *   keep  = word >= T ;  scale = 1.0f / (1.0f - rate) ;  out = keep ? x * scale : 0
+ *
+ * j depends on the logical shape alone: never on strides, tiling or launch geometry.  rate = 0
+ * gives T = 0, scale = 1: a bit-exact copy.
+ *   rate   one float in DEVICE memory, read when the kernel runs (a captured launch follows later
+ *          changes of the rate)
+ *   state  four 32-bit words in DEVICE memory, 16-byte aligned, owned by the caller:
+ *          [0] lo32(seed), [1] hi32(seed), [2] counter, [3] unused; read when the kernel runs
+ *   stream a launch argument: tells the dropout nodes of one model (and the ranks of a
+ *          data-parallel group) apart
+ * e2_dropout_fwd: out = gate(x); e2_dropout_bwd: dx = gate(dout), the same gate for the same
+ * (state, stream).  The two views of a call have identical sizes and may be the same (in place);
+ * otherwise they must not overlap.  One thread makes one Philox block = four consecutive j and
+ * moves them with one 16-byte access where they lie in one 16-byte aligned row piece.
+ * e2_dropout_tick: state[2] += 1 (one tiny launch).  A step issues it once, in front of all its
+ * dropout launches, which then read the counter it left: every replay of a captured step draws
+ * new gates, forward and backward of one step draw the same. */
+int e2_dropout_fwd(e2_ctx*, const e2_tensor5* x, const e2_tensor5* out, int feature_mode,
+                   const float* rate, const void* state, uint32_t stream);
+int e2_dropout_bwd(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* dx, int feature_mode,
+                   const float* rate, const void* state, uint32_t stream);
+int e2_dropout_tick(e2_ctx*, void* state);
+
 #ifdef __cplusplus
 }
 #endif
