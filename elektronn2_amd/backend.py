@@ -22,7 +22,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # made by `make BUILD=... OUT=...`; the product build is never overwritten by experiments)
 LIB_PATH = os.environ.get("E2HIP_LIB") or os.path.join(_HERE, "libe2hip.so")
 
-ACT = {"lin": 0, "relu": 1}
+# computations.py:57-134 apply_activation (E2_ACT_* of include/e2hip.h).  'lin' and 'relu' are
+# taken by every entry point with an `act`; the others by act_fwd / act_bwd alone.
+ACT = {"lin": 0, "linear": 0, "relu": 1, "tanh": 2, "sigmoid": 3, "sig": 3, "logistic": 3,
+       "abs": 4, "elu": 5, "selu": 6, "soft+": 7}
 
 
 class E2Error(RuntimeError):
@@ -198,6 +201,8 @@ def _load():
         "e2_dropout_fwd": (C.c_int, [vp, P5, P5, i, fp, vp, C.c_uint32]),
         "e2_dropout_bwd": (C.c_int, [vp, P5, P5, i, fp, vp, C.c_uint32]),
         "e2_dropout_tick": (C.c_int, [vp, vp]),
+        "e2_act_fwd": (C.c_int, [vp, P5, fp, i, P5]),
+        "e2_act_bwd": (C.c_int, [vp, P5, P5, fp, i, P5, fp]),
         "e2_adam_step": (C.c_int, [vp, fp, fp, fp, fp, sz, vp, fp, i, fp]),
         "e2_sgd_step": (C.c_int, [vp, fp, fp, fp, sz, vp, fp, i, fp]),
         "e2_set_loss_grad_mode": (C.c_int, [vp, i, fp]),
@@ -595,6 +600,17 @@ class Context:
         _chk(_lib.e2_pool_bias_act_bwd(self.h, C.byref(t5(dout)), C.byref(t5(y)), _fp(bias),
                                        pool[0], pool[1], pool[2], ACT[act], C.byref(t5(dy)),
                                        _fp(dbias)), "e2_pool_bias_act_bwd")
+
+    def act_fwd(self, pre, bias, act, out):
+        """out = f(pre + bias[c]) for every name of ACT; bias may be None, out may be pre"""
+        _chk(_lib.e2_act_fwd(self.h, C.byref(t5(pre)), _fp(bias), ACT[act], C.byref(t5(out))),
+             "e2_act_fwd")
+
+    def act_bwd(self, dout, pre, bias, act, dpre, dbias):
+        """dpre = dout * f'(pre + bias[c]), dbias[c] += sum(dpre) (None: not wanted); dpre may
+        be dout"""
+        _chk(_lib.e2_act_bwd(self.h, C.byref(t5(dout)), C.byref(t5(pre)), _fp(bias), ACT[act],
+                             C.byref(t5(dpre)), _fp(dbias)), "e2_act_bwd")
 
     def maxpool3d_fwd(self, x, pool, out):
         _chk(_lib.e2_maxpool3d_fwd(self.h, C.byref(t5(x)), pool[0], pool[1], pool[2],

@@ -22,9 +22,18 @@ include/e2hip.h).  A node with dropout keeps off the routes that never materiali
 tensors (fused head, tail, activation backward inside a consumer's launch, gradient slabs,
 bf16 operand images written by the producer); a node without it is untouched.
 
+Activations (``activation_func=`` of Conv / UpConv / Perceptron, computations.py:57-134):
+'relu' and 'lin' are fused into the pooling kernels and GEMM epilogues.  'tanh', 'sigmoid' (=
+'sig', 'logistic'), 'abs', 'elu', 'selu' and 'soft+' run as an op of their own (csrc/act.hip):
+such a node issues the launches it would issue with 'lin', which leave the pre-activation in a
+buffer, then e2_act_fwd; its backward starts with e2_act_bwd from that buffer and goes on as
+the 'lin' backward.  It keeps off every route that does not leave the pre-activation behind or
+hard-wires relu (fused first layer, fused epilogue, tail, activation backward inside a consumer's
+launch, split-K slabs, bf16 operands made ahead); NeuralLayer._plain_act() is the one predicate.
+
 Outside the hot path and therefore rejected with NotImplementedError here:
-gradnet, batch_normalisation='fadeout', activations other than 'relu' / 'lin',
-conv modes other than 'valid', 1-D convolutions.
+gradnet, batch_normalisation='fadeout', the activations 'prelu', 'maxout <i>', 'concentration'
+and 'radius', conv modes other than 'valid', 1-D convolutions.
 """
 from __future__ import annotations
 
@@ -43,7 +52,17 @@ logger = logging.getLogger('elektronn2log')
 __all__ = ['Conv', 'UpConv', 'Pool', 'Crop', 'AutoMerge', 'UpConvMerge', 'NeuralLayer',
            'FragmentsToDense', 'Perceptron']
 
-_HIP_ACTS = ('relu', 'lin')
+# fused into the pooling kernels / GEMM epilogues; and those that run through csrc/act.hip
+_PLAIN_ACTS = ('relu', 'lin', 'linear')
+_HIP_ACTS = _PLAIN_ACTS + ('tanh', 'sigmoid', 'sig', 'logistic', 'abs', 'elu', 'selu', 'soft+')
+
+
+def check_activation(activation_func):
+    """computations.py:57-134 minus the functions with a parameter of their own ('prelu'), a
+    changed feature count ('maxout <i>') and the two ad-hoc ones ('concentration', 'radius')"""
+    if activation_func not in _HIP_ACTS:
+        raise NotImplementedError("activation_func=%r: only %s are on the HIP hot path"
+                                  % (activation_func, _HIP_ACTS))
 
 
 def check_dropout_rate(rate):
@@ -61,6 +80,17 @@ class NeuralLayer(Node):
     # dropout gate per output element (Conv, UpConv: neural.py:714-720, 1064-1070); the
     # Perceptron draws one per output feature (neural.py:391-397)
     _drop_per_feature = False
+
+    def _plain_act(self):
+        """relu / lin: bias + activation live in the pooling kernels and GEMM epilogues.  Any
+        other activation runs as e2_act_fwd / e2_act_bwd on the materialised pre-activation, and
+        the node stays off every route that fuses the activation away."""
+        return self.activation_func in _PLAIN_ACTS
+
+    def _lin_act(self):
+        """the activation to hand to the node's own kernels: its own when they can fuse it,
+        'lin' when the act pair follows"""
+        return self.activation_func if self._plain_act() else 'lin'
 
     def _drop_fwd(self, plan):
         """dropout, the last thing a node does to its output (neural.py:712-722): in place on
@@ -264,9 +294,7 @@ class Conv(NeuralLayer):
         if conv_mode != 'valid':
             raise NotImplementedError("conv_mode=%r: only 'valid' is on the HIP hot path"
                                       % (conv_mode,))
-        if activation_func not in _HIP_ACTS:
-            raise NotImplementedError("activation_func=%r: only %s are on the HIP hot path"
-                                      % (activation_func, _HIP_ACTS))
+        check_activation(activation_func)
         self.conv_dim = conv_dim
         self.w_sh = w_sh
         self._setup_params(w_sh, w, b, gamma, mean, std, dropout_rate, self.pool_shape,
@@ -378,7 +406,8 @@ class Conv(NeuralLayer):
         node keeps this route: the pair materialises the node's output and reads its output
         gradient, the two tensors the gate is applied to; the backward kernel recomputes the
         pre-activation from x and never reads the gated output.)"""
-        return (not self._bn() and self.parent.is_source and self.parent.shape['f'] == 1 and
+        return (not self._bn() and self._plain_act() and
+                self.parent.is_source and self.parent.shape['f'] == 1 and
                 plan.ctx.conv1_supported(1, self._k3, self._p3) and
                 not plan.needs_grad(self.parent) and not self._mfp_pool())
 
@@ -471,7 +500,8 @@ class Conv(NeuralLayer):
         """no pooling and a specialised kernel width: bias + activation go into the
         conv kernel's epilogue, the pre-activation is never stored"""
         if not (all(p == 1 for p in self._p3) and self._k3[2] in (1, 3, 4, 5)
-                and type(self) is Conv and not self._bn() and not self._fused_first(plan)):
+                and type(self) is Conv and not self._bn() and self._plain_act()
+                and not self._fused_first(plan)):
             return False
         # the fused epilogue cannot split K: only where the output alone yields enough
         # work-groups to fill the chip (small late layers keep split-K + pointwise pass)
@@ -486,6 +516,7 @@ class Conv(NeuralLayer):
         its bias + activation (+ pooling) kernels add them up (e2hip.h, "split-K without
         atomics")"""
         return (type(self) is Conv and not self._bn() and not self._mfp_pool()
+                and self._plain_act()     # (the act pair reads ONE pre-activation / gradient)
                 and tuple(self._p3) in self._PART_WINDOWS and not self._fused_first(plan)
                 and self._fused_head(plan) is None and not plan.fuse_actbwd)
 
@@ -554,6 +585,14 @@ class Conv(NeuralLayer):
                 if plan.training:
                     plan.scratch[self, 'dlin'] = plan.empty(plan.out_shape(self))
             plan.scratch[self, 'bn_save'] = plan.zeros_flat(2 * self.n_f)
+        if not self._plain_act() and plan.training:
+            # what e2_act_bwd reads: the batch-normalised / pooled pre-activation (an un-pooled
+            # conv without batch norm has it in `y` already)
+            if self._bn():
+                plan.scratch[self, 'pre'] = plan.empty(plan.out_shape(self))
+            elif any(p != 1 for p in self._p3):
+                plan.scratch[self, 'lin'] = plan.empty(plan.out_shape(self))
+                plan.scratch[self, 'dlin'] = plan.empty(plan.out_shape(self))
         cin = self.parent.shape['f']
         nb = plan.ctx.conv_ws_bytes(self.n_f, cin, k)
         plan.scratch[self, 'wp_f'] = plan.zeros_flat(nb // 4 + 64)   # padding stays zero
@@ -695,10 +734,13 @@ class Conv(NeuralLayer):
             train = self.batch_normalisation == 'train'
             # the running statistics are extra updates of the OPTIMISER's step function
             # (model.py:180-192), not of loss / prediction / gradient functions
+            pre = plan.scratch.get((self, 'pre'), plan.out[self])
             ctx.batchnorm_act_fwd(lin, plan.param(self.gamma), plan.param(self.b),
                                   plan.param(self.mean), plan.param(self.std), train,
-                                  train and plan.step in ('SGD', 'Adam'), self.activation_func,
-                                  plan.out[self], plan.scratch[self, 'bn_save'])
+                                  train and plan.step in ('SGD', 'Adam'), self._lin_act(),
+                                  pre, plan.scratch[self, 'bn_save'])
+            if not self._plain_act():
+                ctx.act_fwd(pre, None, self.activation_func, plan.out[self])
             return
         if self._mfp_pool():
             # fragment i = max-pool of the conv output shifted by the i-th offset inside the
@@ -710,7 +752,20 @@ class Conv(NeuralLayer):
             for i, (iz, ix, iy) in enumerate(product(range(pz), range(px), range(py))):
                 src = y[:, :, iz:iz + D - pz + 1, ix:ix + H - px + 1, iy:iy + W - py + 1]
                 ctx.pool_bias_act_fwd(src, plan.param(self.b), self._p3,
-                                      self.activation_func, out[i * n_in:(i + 1) * n_in])
+                                      self._lin_act(), out[i * n_in:(i + 1) * n_in])
+            if not self._plain_act():
+                ctx.act_fwd(out, None, self.activation_func, out)
+            return
+        if not self._plain_act():
+            out = plan.out[self]
+            if all(p == 1 for p in self._p3):
+                ctx.act_fwd(y, plan.param(self.b), self.activation_func, out)
+            elif (self, 'lin') in plan.scratch:      # a training plan keeps the pooled sum
+                ctx.maxpool3d_fwd(y, self._p3, plan.scratch[self, 'lin'])
+                ctx.act_fwd(plan.scratch[self, 'lin'], plan.param(self.b), self.activation_func, out)
+            else:
+                ctx.pool_bias_act_fwd(y, plan.param(self.b), self._p3, 'lin', out)
+                ctx.act_fwd(out, None, self.activation_func, out)
             return
         ndst = bf16_ahead.next_dst(plan, self)
         if ndst is not None:
@@ -753,12 +808,26 @@ class Conv(NeuralLayer):
             pooled = any(p != 1 for p in self._p3)
             lin = plan.scratch[self, 'lin'] if pooled else plan.scratch[self, 'y']
             dlin = plan.scratch[self, 'dlin'] if pooled else dy
+            if not self._plain_act():          # in place on the output gradient
+                ctx.act_bwd(plan.grad[self], plan.scratch[self, 'pre'], None, self.activation_func,
+                            plan.grad[self], None)
             ctx.batchnorm_act_bwd(plan.grad[self], lin, plan.param(self.gamma),
                                   plan.param(self.b), plan.scratch[self, 'bn_save'], train,
-                                  self.activation_func, dlin,
+                                  self._lin_act(), dlin,
                                   plan.pgrad(self.gamma) if self.gamma.apply_train else None,
                                   plan.pgrad(self.b))
             if pooled:
+                ctx.maxpool3d_bwd(dlin, plan.scratch[self, 'y'], self._p3, dy)
+        elif not self._plain_act():
+            # slope from the pre-activation the forward kept; then the 'lin' backward
+            g = plan.grad[self]
+            if all(p == 1 for p in self._p3):
+                ctx.act_bwd(g, plan.scratch[self, 'y'], plan.param(self.b), self.activation_func,
+                            dy, plan.pgrad(self.b))
+            else:                              # ... of the pooled sum, then un-pool
+                dlin = plan.scratch[self, 'dlin']
+                ctx.act_bwd(g, plan.scratch[self, 'lin'], plan.param(self.b),
+                            self.activation_func, dlin, plan.pgrad(self.b))
                 ctx.maxpool3d_bwd(dlin, plan.scratch[self, 'y'], self._p3, dy)
         elif plan.scratch.get((self, 'dy_done')) or plan.scratch.get((self, 'dy_by_tail')):
             pass        # the consumer's data-gradient launch (below) or the tail launch
@@ -939,9 +1008,7 @@ class Perceptron(NeuralLayer):
         self.axis = parent.shape.tag2index('f')
         self.flatten = flatten
         self.spatial_axes = parent.shape.spatial_axes
-        if activation_func not in _HIP_ACTS:
-            raise NotImplementedError("activation_func=%r: only %s are on the HIP hot path"
-                                      % (activation_func, _HIP_ACTS))
+        check_activation(activation_func)
         if flatten:
             if self.axis != 1:
                 raise NotImplementedError("Cannot flatten tensor for "
@@ -980,6 +1047,8 @@ class Perceptron(NeuralLayer):
             plan.scratch[self, 'dlin'] = plan.empty(plan.out_shape(self))
         if self._bn():
             plan.scratch[self, 'bn_save'] = plan.zeros_flat(2 * self.n_f)
+            if not self._plain_act() and plan.training:
+                plan.scratch[self, 'pre'] = plan.empty(plan.out_shape(self))
 
     def _x2(self, plan, t):
         """the parent's buffer as the (batch, n_in) matrix"""
@@ -994,10 +1063,15 @@ class Perceptron(NeuralLayer):
                       lin.reshape(lin.shape[0], -1))
         if self._bn():
             train = self.batch_normalisation == 'train'
+            pre = plan.scratch.get((self, 'pre'), plan.out[self])
             ctx.batchnorm_act_fwd(lin, plan.param(self.gamma), plan.param(self.b),
                                   plan.param(self.mean), plan.param(self.std), train,
-                                  train and plan.step in ('SGD', 'Adam'), self.activation_func,
-                                  plan.out[self], plan.scratch[self, 'bn_save'])
+                                  train and plan.step in ('SGD', 'Adam'), self._lin_act(),
+                                  pre, plan.scratch[self, 'bn_save'])
+            if not self._plain_act():
+                ctx.act_fwd(pre, None, self.activation_func, plan.out[self])
+        elif not self._plain_act():
+            ctx.act_fwd(lin, plan.param(self.b), self.activation_func, plan.out[self])
         else:
             ctx.pool_bias_act_fwd(lin, plan.param(self.b), (1, 1, 1), self.activation_func,
                                   plan.out[self])
@@ -1006,11 +1080,17 @@ class Perceptron(NeuralLayer):
         ctx = plan.ctx
         lin, dlin = plan.scratch[self, 'lin'], plan.scratch[self, 'dlin']
         if self._bn():
+            if not self._plain_act():          # in place on the output gradient
+                ctx.act_bwd(plan.grad[self], plan.scratch[self, 'pre'], None, self.activation_func,
+                            plan.grad[self], None)
             ctx.batchnorm_act_bwd(plan.grad[self], lin, plan.param(self.gamma),
                                   plan.param(self.b), plan.scratch[self, 'bn_save'],
-                                  self.batch_normalisation == 'train', self.activation_func,
+                                  self.batch_normalisation == 'train', self._lin_act(),
                                   dlin, plan.pgrad(self.gamma) if self.gamma.apply_train else None,
                                   plan.pgrad(self.b))
+        elif not self._plain_act():
+            ctx.act_bwd(plan.grad[self], lin, plan.param(self.b), self.activation_func, dlin,
+                        plan.pgrad(self.b))
         else:
             ctx.pool_bias_act_bwd(plan.grad[self], lin, plan.param(self.b), (1, 1, 1),
                                   self.activation_func, dlin, plan.pgrad(self.b))
@@ -1113,6 +1193,11 @@ class UpConv(Conv):
 
     def _plan_alloc(self, plan):
         plan.alloc_out(self)
+        if not self._plain_act() and plan.training and plan.needs_grad(self):
+            # bias + 'lin' land here, e2_act_fwd carries them to the output (a Concat slice or
+            # not); the backward takes the slope from it -- not from the output, as the relu
+            # form does, which cannot tell the sign of abs's argument
+            plan.scratch[self, 'pre'] = plan.empty(plan.out_shape(self))
         xs = plan.out_shape(self.parent)
         cin = self.parent.shape['f']
         nb = plan.ctx.upconv_ws_bytes(self.n_f, cin, self.pool_shape, xs)
@@ -1148,17 +1233,19 @@ class UpConv(Conv):
         if wp is not None:
             plan.join_side()                  # (the repack may run on the side stream)
 
+        pre = plan.scratch.get((self, 'pre'), plan.out[self])
+
         def run():
             if wp is not None:
                 plan.ctx.upconv3d_fwd_packed(plan.out[self.parent], wp, plan.param(self.b),
-                                             self.n_f, self.pool_shape, self.activation_func,
-                                             plan.out[self])
+                                             self.n_f, self.pool_shape, self._lin_act(), pre)
             else:
                 plan.ctx.upconv3d_fwd(plan.out[self.parent], plan.param(self.w),
                                       plan.param(self.b), self.pool_shape,
-                                      self.activation_func, plan.out[self],
-                                      plan.scratch[self, 'ws'])
+                                      self._lin_act(), pre, plan.scratch[self, 'ws'])
         plan.tuned('igemm', sig, cands, run)
+        if not self._plain_act():
+            plan.ctx.act_fwd(pre, None, self.activation_func, plan.out[self])
 
     def _plan_bwd(self, plan):
         ctx = plan.ctx
@@ -1174,16 +1261,20 @@ class UpConv(Conv):
         sigs = self._tune_sigs(plan)
         wp_d = plan.scratch.get((self, 'wp_d'))
         packed = (self, 'wp_f') in plan.scratch and (dx is None or wp_d is not None)
+        if not self._plain_act():
+            # once, in place on the output gradient and outside the tuner's repeated `run`
+            ctx.act_bwd(plan.grad[self], plan.scratch[self, 'pre'], None, self.activation_func,
+                        plan.grad[self], None)
 
         def run():
             if packed:
                 ctx.upconv3d_bwd_packed(plan.out[self.parent], wp_d, plan.out[self],
-                                        plan.grad[self], self.pool_shape, self.activation_func,
+                                        plan.grad[self], self.pool_shape, self._lin_act(),
                                         dx, plan.pgrad(self.w), plan.pgrad(self.b),
                                         plan.scratch[self, 'ws'], accumulate=plan._capturing)
             else:
                 ctx.upconv3d_bwd(plan.out[self.parent], plan.param(self.w), plan.out[self],
-                                 plan.grad[self], self.pool_shape, self.activation_func, dx,
+                                 plan.grad[self], self.pool_shape, self._lin_act(), dx,
                                  plan.pgrad(self.w), plan.pgrad(self.b), plan.scratch[self, 'ws'])
         plan.tuned('igemm', sigs['dgrad'][0], sigs['dgrad'][1] if dx is not None else [],
                    lambda: plan.tuned('wgrad', sigs['wgrad'][0], sigs['wgrad'][1], run))

@@ -46,7 +46,10 @@ typedef struct e2_tensor5 {
   int64_t sn, sc, sd, sh;
 } e2_tensor5;
 
-enum { E2_ACT_LIN = 0, E2_ACT_RELU = 1 };
+/* computations.py:57-134 apply_activation.  Every entry point that takes an `act` accepts LIN and
+ * RELU; the values behind them are taken by e2_act_fwd / e2_act_bwd alone. */
+enum { E2_ACT_LIN = 0, E2_ACT_RELU = 1, E2_ACT_TANH, E2_ACT_SIGMOID, E2_ACT_ABS,
+       E2_ACT_ELU, E2_ACT_SELU, E2_ACT_SOFTPLUS };
 enum { E2_MFMA_F32 = 0, E2_MFMA_BF16 = 1 };
 enum { E2_TILING_IGEMM = 0, E2_TILING_WGRAD = 1 };
 
@@ -803,6 +806,33 @@ int e2_dropout_fwd(e2_ctx*, const e2_tensor5* x, const e2_tensor5* out, int feat
 int e2_dropout_bwd(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* dx, int feature_mode,
                    const float* rate, const void* state, uint32_t stream);
 int e2_dropout_tick(e2_ctx*, void* state);
+
+/* ---- bias + activation as an op of its own (computations.py:57-134 apply_activation, called
+ *      from neural.py:389 Perceptron, :712 Conv, :1062 UpConv) -------------------------------
+ * All eight E2_ACT_* values, on strided views of identical sizes; v = pre + bias[c]:
+ *
+ *   act       f(v)                                  f'(v)
+ *   LIN       v                                     1
+ *   RELU      max(v, 0)                             v > 0 ? 1 : (v == 0 ? 0.5 : 0)
+ *   TANH      tanh v                                1 - tanh^2 v
+ *   SIGMOID   1 / (1 + e^-v)                        f (1 - f)
+ *   ABS       |v|                                   sgn v, 0 at v = 0
+ *   ELU       v > 0 ? v : expm1 v                   v > 0 ? 1 : e^v
+ *   SELU      s (v > 0 ? v : a expm1 v)             v > 0 ? s : s a e^v
+ *             a = 1.6732632423543772..., s = 1.0507009873554804... (computations.py:96-98)
+ *   SOFTPLUS  log(1 + e^v)                          sigmoid v
+ *
+ * The slopes at v = 0 follow the reading of Theano that gives relu'(0) = 0.5 (T.nnet.relu =
+ * 0.5 (v + |v|), sgn 0 = 0): abs'(0) = 0; switch(v > 0, ..) takes its second branch at 0, so
+ * elu'(0) = 1 and selu'(0) = s a.  f32 arithmetic in forms that are finite for every finite v.
+ * Nodes with relu / lin do not use this pair (their activation is fused into the pooling
+ * kernels and GEMM epilogues); both values are accepted so that the op is complete. */
+/* out = f(pre + bias[c]);  bias may be NULL;  out may alias pre (computations.py:57-134) */
+int e2_act_fwd(e2_ctx*, const e2_tensor5* pre, const float* bias, int act, const e2_tensor5* out);
+/* dpre = dout * f'(pre + bias[c]);  dbias[c] += sum over n,z,y,x of dpre (NULL: not wanted; the
+ * caller zeroes it);  dpre may alias dout (T.grad of computations.py:57-134) */
+int e2_act_bwd(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* pre, const float* bias, int act,
+               const e2_tensor5* dpre, float* dbias);
 
 #ifdef __cplusplus
 }
