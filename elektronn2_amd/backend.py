@@ -67,6 +67,17 @@ class NllWeights(C.Structure):
                 ("labelled", C.c_void_p), ("not_present", C.c_void_p)]
 
 
+class LossTerm(C.Structure):
+    """e2_loss_term (include/e2hip.h): one element-wise loss of a mix; kind = LOSS[...]"""
+    _fields_ = [("kind", C.c_int), ("margin", C.c_void_p), ("scale_correction", C.c_void_p),
+                ("subtract_label_entropy", C.c_int), ("sig_is_log", C.c_int)]
+
+
+# E2_LOSS_* of include/e2hip.h
+LOSS = {"squared": 0, "abs": 1, "binary_nll": 2, "gauss_nll": 3}
+MAX_LOSS_TERMS = 8
+
+
 def t5_shape(shape):
     """a Tensor5 that carries extents only (null pointer): the shape argument of the entry points
     whose operand was made ahead of the call"""
@@ -83,6 +94,7 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     P5 = C.POINTER(Tensor5)
     PW = C.POINTER(NllWeights)
+    PL = C.POINTER(LossTerm)
     vp, i, sz, fp = C.c_void_p, C.c_int, C.c_size_t, C.c_void_p
     sig = {
         "e2_ctx_create": (C.c_int, [i, C.POINTER(vp)]),
@@ -203,6 +215,11 @@ def _load():
         "e2_dropout_tick": (C.c_int, [vp, vp]),
         "e2_act_fwd": (C.c_int, [vp, P5, fp, i, P5]),
         "e2_act_bwd": (C.c_int, [vp, P5, P5, fp, i, P5, fp]),
+        "e2_loss_partials": (sz, [vp, P5]),
+        "e2_loss_fwd": (C.c_int, [vp, PL, P5, P5, P5, fp]),
+        "e2_loss_mix": (C.c_int, [vp, i, PL, C.POINTER(C.c_void_p), C.POINTER(sz),
+                                  C.POINTER(C.c_int64), fp, fp, fp, fp, fp]),
+        "e2_loss_bwd": (C.c_int, [vp, PL, P5, P5, P5, fp, P5, P5, i]),
         "e2_adam_step": (C.c_int, [vp, fp, fp, fp, fp, sz, vp, fp, i, fp]),
         "e2_sgd_step": (C.c_int, [vp, fp, fp, fp, sz, vp, fp, i, fp]),
         "e2_set_loss_grad_mode": (C.c_int, [vp, i, fp]),
@@ -275,6 +292,22 @@ def nll_weights(class_w=None, example_w=None, labelled=None, not_present=None):
     w.labelled = _fp(labelled)
     w.not_present = _fp(not_present)
     return w
+
+
+def loss_term(kind, margin=None, scale_correction=None, subtract_label_entropy=False,
+              sig_is_log=False):
+    """an e2_loss_term descriptor: ``kind`` a key of LOSS; ``margin`` / ``scale_correction`` one-
+    element device tensors (None: absent) that the kernels read when they RUN."""
+    if kind not in LOSS:
+        raise ValueError("loss_term: unknown kind %r (one of %s)" % (kind, sorted(LOSS)))
+    t = LossTerm()
+    t._keep = (margin, scale_correction)                      # (the tensors outlive the descriptor)
+    t.kind = LOSS[kind]
+    t.margin = _fp(margin)
+    t.scale_correction = _fp(scale_correction)
+    t.subtract_label_entropy = int(bool(subtract_label_entropy))
+    t.sig_is_log = int(bool(sig_is_log))
+    return t
 
 
 def _fp(t: Optional[torch.Tensor]):
@@ -605,6 +638,49 @@ class Context:
         """out = f(pre + bias[c]) for every name of ACT; bias may be None, out may be pre"""
         _chk(_lib.e2_act_fwd(self.h, C.byref(t5(pre)), _fp(bias), ACT[act], C.byref(t5(out))),
              "e2_act_fwd")
+
+    # ---- element-wise losses and their mix (csrc/loss_elem.hip) ---------------------------------
+    def loss_partials(self, pred):
+        """rows of 4 floats that loss_fwd writes for this prediction"""
+        n = int(_lib.e2_loss_partials(self.h, C.byref(t5(pred))))
+        if n <= 0:
+            raise E2Error("e2_loss_partials: empty prediction %s" % (tuple(pred.shape),))
+        return n
+
+    def loss_fwd(self, term, pred, sig, target, partials):
+        """per-work-group sums (S1, n_lab, S2, 0) of one loss term into ``partials`` (rows, 4)"""
+        if partials.numel() < 4 * self.loss_partials(pred):
+            raise E2Error("loss_fwd: the partials slab is too small for this prediction")
+        _chk(_lib.e2_loss_fwd(self.h, C.byref(term), C.byref(t5(pred)),
+                              None if sig is None else C.byref(t5(sig)), C.byref(t5(target)),
+                              _fp(partials)), "e2_loss_fwd")
+
+    def loss_mix(self, terms, partials, n_tot, mix, coef, term_loss, count, loss_out):
+        """slabs of the k terms -> term_loss[k], count[k], coef[k] and the total loss_out[0]"""
+        k = len(terms)
+        if not (len(partials) == len(n_tot) == k):
+            raise E2Error("loss_mix: %d terms, %d slabs, %d sizes" % (k, len(partials), len(n_tot)))
+        if k > MAX_LOSS_TERMS:
+            raise E2Error("loss_mix: %d terms, at most %d are supported" % (k, MAX_LOSS_TERMS))
+        for t in (mix, coef, term_loss, count):
+            if t.numel() < k:
+                raise E2Error("loss_mix: mix / coef / term_loss / count need %d floats" % k)
+        if loss_out.numel() < 1:
+            raise E2Error("loss_mix: loss_out needs one float")
+        ta = (LossTerm * max(k, 1))(*terms)
+        pa = (C.c_void_p * max(k, 1))(*[_fp(p) for p in partials])
+        ra = (C.c_size_t * max(k, 1))(*[int(p.numel()) // 4 for p in partials])
+        na = (C.c_int64 * max(k, 1))(*[int(n) for n in n_tot])
+        _chk(_lib.e2_loss_mix(self.h, k, ta, pa, ra, na, _fp(mix), _fp(coef), _fp(term_loss),
+                              _fp(count), _fp(loss_out)), "e2_loss_mix")
+
+    def loss_bwd(self, term, pred, sig, target, coef, dpred, dsig=None, accumulate=False):
+        """dpred (=|+=) coef * d(term sum)/d(pred) (GAUSS_NLL: also dsig); ``coef`` the one-element
+        device tensor loss_mix wrote for the term"""
+        opt = lambda t: None if t is None else C.byref(t5(t))
+        _chk(_lib.e2_loss_bwd(self.h, C.byref(term), C.byref(t5(pred)), opt(sig),
+                              C.byref(t5(target)), _fp(coef), opt(dpred), opt(dsig),
+                              int(bool(accumulate))), "e2_loss_bwd")
 
     def act_bwd(self, dout, pre, bias, act, dpre, dbias):
         """dpre = dout * f'(pre + bias[c]), dbias[c] += sum(dpre) (None: not wanted); dpre may

@@ -5,8 +5,8 @@ from .variables import VariableParam, VariableWeight, ConstantParam, initweights
 from .node_basic import (Node, Input, Input_like, Concat, Add, model_manager,
                          choose_name)
 from .neural import Conv, UpConv, Pool, Crop, AutoMerge, UpConvMerge, FragmentsToDense, Perceptron
-from .loss import (Softmax, MultinoulliNLL, MalisNLL, AggregateLoss, Classification,
-                   Errors)
+from .loss import (Softmax, MultinoulliNLL, MalisNLL, SquaredLoss, AbsLoss, BinaryNLL,
+                   GaussianNLL, AggregateLoss, Classification, Errors)
 from .optimiser import Optimiser, SGD, Adam
 from .model import Model, modelload, params_from_model_file
 from .options import set_plan_options, plan_options

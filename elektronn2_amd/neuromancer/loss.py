@@ -1,6 +1,6 @@
-"""Softmax / MultinoulliNLL / AggregateLoss / Errors with the reference's
-constructor signatures (elektronn2/neuromancer/loss.py:33-93, 141-351,
-693-826, 1279-1370).
+"""Softmax / MultinoulliNLL / SquaredLoss / AbsLoss / BinaryNLL / GaussianNLL / AggregateLoss /
+Errors with the reference's constructor signatures (elektronn2/neuromancer/loss.py:33-93,
+141-351, 693-826, 829-887, 953-1101, 1215-1370).
 
 HIP execution covers the pattern every BASELINE config uses:
 ``AggregateLoss(MultinoulliNLL(Softmax(lin-Conv), target, target_is_sparse=True))``
@@ -25,6 +25,18 @@ outside the hot path and raise NotImplementedError.  ``Softmax(n_indep > 1)`` (i
 consecutive feature groups, loss.py:82-92) exists for ``MalisNLL`` (loss.py:560-690,
 SURVEY.md 8f-4): forward and gradient on the device, the MALIS counts by the host C++
 of csrc/malis.cpp between the forward and the backward segment of the step.
+
+Element-wise losses (csrc/loss_elem.hip): ``SquaredLoss``, ``AbsLoss``, ``BinaryNLL``,
+``GaussianNLL`` over any prediction node whose output the plan materialises (a Conv with any
+activation, UpConv, Perceptron, a Concat ...), with a target of the prediction's shape, and
+``AggregateLoss`` over 1..8 of them with ``mixing_weights``:
+    total = (1/K) sum_k w_k L_k,   L_k as in the table of include/e2hip.h ("element-wise losses").
+Each term is one forward launch that leaves per-work-group sums in a slab; the AggregateLoss node
+owns one small launch that turns the slabs into the term values, the labelled counts, the gradient
+coefficients and the total; each term's backward launch writes (or adds to) its prediction's output
+gradient.  ``margin``, ``scale_correction`` and ``mixing_weights`` are non-trainable parameters the
+kernels read in place.  Mixing these with a MultinoulliNLL / MalisNLL raises NotImplementedError
+(their fused launches take no scale), and so does the ``'s'`` sample axis.
 """
 from __future__ import annotations
 
@@ -34,8 +46,10 @@ from .graphutils import TaggedShape, floatX
 from .node_basic import Node, Sym
 from .variables import VariableParam
 
-__all__ = ['Softmax', 'MultinoulliNLL', 'MalisNLL', 'AggregateLoss', 'Classification',
-           'Errors']
+__all__ = ['Softmax', 'MultinoulliNLL', 'MalisNLL', 'SquaredLoss', 'AbsLoss', 'BinaryNLL',
+           'GaussianNLL', 'AggregateLoss', 'Classification', 'Errors']
+
+MAX_LOSS_TERMS = 8     # E2_MAX_LOSS_TERMS of include/e2hip.h
 
 EPS = 1e-5     # loss.py:30
 
@@ -401,6 +415,187 @@ class MalisNLL(Node):
         return plan.scratch[self, 'loss'][0]
 
 
+class _ElementLoss(Node):
+    """What SquaredLoss / AbsLoss / BinaryNLL / GaussianNLL share: one term of an AggregateLoss
+    that runs as e2_loss_fwd -> (the aggregate's e2_loss_mix) -> e2_loss_bwd.  After a step
+    ``term_value`` (this term's L, before the mixing weight) and ``n_labelled`` hold what the
+    reference shows among its ``_debug_outputs``."""
+    kind = None
+
+    def _check_shapes(self, pred, others):
+        if 's' in pred.shape.tags:
+            raise NotImplementedError("%s: the 's' sample axis is outside the HIP hot path"
+                                      % type(self).__name__)
+        for what, n in others:
+            if tuple(n.shape.shape) != tuple(pred.shape.shape) or \
+                    tuple(n.shape.tags) != tuple(pred.shape.tags):
+                raise ValueError("%s: the %s must have the prediction's shape %s, got %s"
+                                 % (type(self).__name__, what, pred.shape, n.shape))
+        self._last_plan = None
+
+    def _calc_comp_cost(self):
+        self.computational_cost = self.parent[0].shape.stripnone_prod
+
+    def _views(self, plan):
+        """(pred, sig, target) device views"""
+        return plan.out[self.pred], None, plan.out[self.target]
+
+    def _grad_targets(self):
+        """nodes whose output gradient this term writes: (pred,) or (mu, sig)"""
+        return (self.pred,)
+
+    def _term(self, plan):
+        """the e2_loss_term descriptor of this plan: names the parameters' slices of the
+        parameter arena, which the kernels read when they run (no new capture for new values)"""
+        t = plan.scratch.get((self, 'term'))
+        if t is None:
+            from .. import backend
+            dev = lambda p: None if p is None else plan.param(p).reshape(-1)
+            t = backend.loss_term(self.kind, margin=dev(getattr(self, 'margin', None)),
+                                  scale_correction=dev(getattr(self, 'scale_correction', None)),
+                                  subtract_label_entropy=getattr(self, 'subtract_label_entropy', False),
+                                  sig_is_log=getattr(self, 'sig_is_log', False))
+            plan.scratch[self, 'term'] = t
+        return t
+
+    def _plan_alloc(self, plan):
+        for n in self.parent:
+            if plan.out.get(n) is None:
+                raise NotImplementedError("%s: the output of '%s' is not materialised by the plan"
+                                          % (type(self).__name__, n.name))
+        pred = plan.out[self.pred]
+        plan.scratch[self, 'partials'] = plan.empty_flat(4 * plan.ctx.loss_partials(pred))
+        plan.scratch[self, 'n_tot'] = int(pred.numel())
+        plan.out[self] = None        # the element-wise array is never materialised
+
+    def _plan_fwd(self, plan):
+        pred, sig, target = self._views(plan)
+        plan.ctx.loss_fwd(self._term(plan), pred, sig, target, plan.scratch[self, 'partials'])
+
+    def _plan_bwd(self, plan):
+        agg = plan.scratch.get((self, 'agg'))
+        if agg is None:
+            raise NotImplementedError("%s '%s' outside an AggregateLoss has no gradient"
+                                      % (type(self).__name__, self.name))
+        node, k = agg
+        coef = plan.scratch[node, 'coef'][k:k + 1]
+        pred, sig, target = self._views(plan)
+        slots = [plan.grad_slot(n) if plan.needs_grad(n) else (None, True)
+                 for n in self._grad_targets()]
+        if len(slots) == 1:
+            slots.append((None, True))
+        (dp, fp), (ds, fs) = slots
+        if dp is None and ds is None:
+            return
+        if dp is not None and ds is not None and fp != fs:
+            # (one of the two buffers already holds another consumer's gradient)
+            plan.ctx.loss_bwd(self._term(plan), pred, sig, target, coef, dp, None, not fp)
+            plan.ctx.loss_bwd(self._term(plan), pred, sig, target, coef, None, ds, not fs)
+            return
+        plan.ctx.loss_bwd(self._term(plan), pred, sig, target, coef, dp, ds,
+                          not (fp if dp is not None else fs))
+
+    def _mix_value(self, what):
+        plan = self._last_plan
+        agg = None if plan is None else plan.scratch.get((self, 'agg'))
+        if agg is None:
+            return None
+        plan.stream.synchronize()
+        return plan.scratch[agg[0], what][agg[1]].item()
+
+    @property
+    def term_value(self):
+        """this term's value L of the last step / evaluation (None before the first)"""
+        v = self._mix_value('term_loss')
+        return None if v is None else np.float32(v)
+
+    @property
+    def n_labelled(self):
+        """unmasked target elements of the last step / evaluation (GaussianNLL: all elements)"""
+        v = self._mix_value('count')
+        return None if v is None else int(round(v))
+
+
+class SquaredLoss(_ElementLoss):
+    """loss.py:1014-1101.  0.5 (target - pred)^2 per element; ``margin``: elements with
+    |target - pred| < margin do not count (and the margin is subtracted, as the reference does);
+    ``scale_correction`` sc: times sc / (|target| + sc).  Targets of -666 are masked.  A falsy
+    ``margin`` / ``scale_correction`` means none (loss.py:1045, 1052)."""
+    kind = 'squared'
+
+    def __init__(self, pred, target, margin=None, scale_correction=None, name="se",
+                 print_repr=True):
+        super(SquaredLoss, self).__init__((pred, target), name, print_repr)
+        self.target = target
+        self.pred = pred
+        self._check_shapes(pred, [('target', target)])
+        if margin:
+            margin = VariableParam(value=margin, name="margin", dtype=floatX, apply_train=False)
+            self.params['margin'] = margin
+        else:
+            margin = None
+        self.margin = margin
+        if scale_correction:
+            scale_correction = VariableParam(value=scale_correction, name="scale_correction",
+                                             dtype=floatX, apply_train=False)
+            self.params['scale_correction'] = scale_correction
+        else:
+            scale_correction = None
+        self.scale_correction = scale_correction
+
+    def _calc_shape(self):
+        self.shape = self.parent[0].shape.updateshape(self.pred.shape.tag2index('f'), 1)
+
+
+class AbsLoss(SquaredLoss):
+    """loss.py:1215-1276.  |target - pred| per element, ``margin`` as for SquaredLoss;
+    ``scale_correction`` sc: times sc |target| + 1.  The slope at target == pred is 0."""
+    kind = 'abs'
+
+    def __init__(self, pred, target, margin=None, scale_correction=None, name="absloss",
+                 print_repr=True):
+        super(AbsLoss, self).__init__(pred, target, margin=margin,
+                                      scale_correction=scale_correction, name=name,
+                                      print_repr=print_repr)
+
+
+class BinaryNLL(_ElementLoss):
+    """loss.py:953-1011.  -(t log(p + EPS) + (1 - t) log(1 - p + EPS)) per element with
+    x log y = 0 where x == 0; ``subtract_label_entropy`` also subtracts the target's own entropy
+    (no gradient).  Targets of -666 are masked."""
+    kind = 'binary_nll'
+
+    def __init__(self, pred, target, subtract_label_entropy=False, name="binary_nll",
+                 print_repr=True):
+        super(BinaryNLL, self).__init__((pred, target), name, print_repr)
+        self.target = target
+        self.pred = pred
+        self.pred_shape = pred.shape
+        self.subtract_label_entropy = bool(subtract_label_entropy)
+        self._check_shapes(pred, [('target', target)])
+
+
+class GaussianNLL(_ElementLoss):
+    """loss.py:829-887.  0.5 log(2 pi) + log sig + 0.5 ((target - mu) / sig)^2 per element;
+    ``sig_is_log``: ``sig`` holds log(sigma).  No mask."""
+    kind = 'gauss_nll'
+
+    def __init__(self, mu, sig, target, sig_is_log=False, name="g_nll", print_repr=True):
+        super(GaussianNLL, self).__init__((mu, sig, target), name, print_repr)
+        self.target = target
+        self.mu = mu
+        self.pred = mu
+        self.sig = sig
+        self.sig_is_log = bool(sig_is_log)
+        self._check_shapes(mu, [('sig', sig), ('target', target)])
+
+    def _views(self, plan):
+        return plan.out[self.mu], plan.out[self.sig], plan.out[self.target]
+
+    def _grad_targets(self):
+        return (self.mu, self.sig)
+
+
 class AggregateLoss(Node):
     def __init__(self, parent_nodes, mixing_weights=None, name="total_loss", print_repr=True):
         if not isinstance(parent_nodes, (tuple, list)):
@@ -419,9 +614,22 @@ class AggregateLoss(Node):
             raise ValueError("Unsupported weight format")
         self.params['mixing_weights'] = mixing_weights
         self.mixing_weights = mixing_weights
-        if len(parent_nodes) != 1 or not isinstance(parent_nodes[0], (MultinoulliNLL, MalisNLL)):
+        # two forms: exactly one MultinoulliNLL / MalisNLL (their own launches make the loss), or
+        # 1..MAX_LOSS_TERMS element-wise losses mixed by this node's launch (csrc/loss_elem.hip)
+        self.elementwise = len(parent_nodes) > 0 and \
+            all(isinstance(n, _ElementLoss) for n in parent_nodes)
+        if self.elementwise:
+            if len(parent_nodes) > MAX_LOSS_TERMS:
+                raise ValueError("AggregateLoss: %i losses given, the HIP hot path mixes at most %i"
+                                 % (len(parent_nodes), MAX_LOSS_TERMS))
+        elif len(parent_nodes) != 1 and any(isinstance(n, (MultinoulliNLL, MalisNLL))
+                                            for n in parent_nodes):
+            raise NotImplementedError("a MultinoulliNLL / MalisNLL cannot be mixed with other "
+                                      "losses: their fused tail / head launches take no scale")
+        elif len(parent_nodes) != 1 or not isinstance(parent_nodes[0], (MultinoulliNLL, MalisNLL)):
             raise NotImplementedError("the HIP hot path aggregates exactly one "
-                                      "MultinoulliNLL / MalisNLL loss")
+                                      "MultinoulliNLL / MalisNLL loss, or 1..%i of SquaredLoss / "
+                                      "AbsLoss / BinaryNLL / GaussianNLL" % MAX_LOSS_TERMS)
 
     def _calc_shape(self):
         self.shape = TaggedShape([1, ], ['f', ])
@@ -431,14 +639,39 @@ class AggregateLoss(Node):
 
     def _plan_alloc(self, plan):
         plan.out[self] = None
+        if self.elementwise:
+            for k, n in enumerate(self.parent):
+                plan.scratch[n, 'agg'] = (self, k)
+                n._last_plan = plan
+            for what in ('coef', 'term_loss', 'count'):
+                plan.scratch[self, what] = plan.zeros_flat(MAX_LOSS_TERMS)
+            plan.scratch[self, 'loss'] = plan.zeros_flat(1)
 
     def _plan_fwd(self, plan):
-        pass
+        if not self.elementwise:
+            return
+        ps = list(self.parent)
+        plan.ctx.loss_mix([n._term(plan) for n in ps], [plan.scratch[n, 'partials'] for n in ps],
+                          [plan.scratch[n, 'n_tot'] for n in ps],
+                          plan.param(self.mixing_weights).reshape(-1), plan.scratch[self, 'coef'],
+                          plan.scratch[self, 'term_loss'], plan.scratch[self, 'count'],
+                          plan.scratch[self, 'loss'])
 
     def _plan_bwd(self, plan):
         pass          # d(total)/d(nll) = mixing_weight(=1) / 1 ; folded into the NLL backward
+                      # (element-wise losses: coef[k], which each term's backward launch reads)
+
+    def loss_dev(self, plan):
+        """the one-element device tensor that holds the step's loss"""
+        if self.elementwise:
+            for n in self.parent:
+                n._last_plan = plan
+            return plan.scratch[self, 'loss']
+        return plan.scratch[self.parent[0], 'loss']
 
     def host_value(self, plan):
+        if self.elementwise:
+            return np.float32(self.loss_dev(plan).item())
         w = float(self.mixing_weights.get_value()[0])
         return np.float32(float(self.parent[0].loss_value(plan).item()) * w)
 

@@ -987,6 +987,11 @@ class Plan(object):
         emit()
 
     def _loss_dev(self):
+        """the one-element device tensor that holds the step's loss: the loss node says where
+        (AggregateLoss.loss_dev); any other loss node keeps it under its first parent"""
+        f = getattr(self.loss_node, 'loss_dev', None)
+        if f is not None:
+            return f(self)
         nll = self.loss_node.parent[0] if isinstance(self.loss_node.parent, (list, tuple)) \
             else self.loss_node.parent
         return self.scratch[nll, 'loss']
@@ -1190,8 +1195,7 @@ class Plan(object):
         with torch.cuda.stream(self.stream):
             for o in self.outputs:
                 if self.training and o is self.loss_node:
-                    nll = o.parent[0] if isinstance(o.parent, (list, tuple)) else o.parent
-                    rets.append(np.float32(self.scratch[nll, 'loss'].item()))
+                    rets.append(np.float32(self._loss_dev().item()))
                 elif hasattr(o, 'host_value'):
                     rets.append(o.host_value(self))
                 elif self.out.get(o) is None:
@@ -1213,9 +1217,7 @@ class Plan(object):
         of the compiled function); this is the opt-in form of Model.trainingstep(sync=False)."""
         if not self.training:
             raise RuntimeError("fetch_async: a training plan is needed")
-        nll = self.loss_node.parent[0] if isinstance(self.loss_node.parent, (list, tuple)) \
-            else self.loss_node.parent
-        dev_loss = self.scratch[nll, 'loss']
+        dev_loss = self._loss_dev()
         if self._async is None:
             self._async = dict(pin=[torch.empty(1, dtype=torch.float32).pin_memory() for _ in range(2)],
                                ev=[torch.cuda.Event(), torch.cuda.Event()], n=0, run=[-1, -1])

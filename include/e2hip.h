@@ -834,6 +834,64 @@ int e2_act_fwd(e2_ctx*, const e2_tensor5* pre, const float* bias, int act, const
 int e2_act_bwd(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* pre, const float* bias, int act,
                const e2_tensor5* dpre, float* dbias);
 
+/* ---- element-wise losses and their mix (loss.py:829-887 GaussianNLL, 953-1011 BinaryNLL,
+ *      1014-1101 SquaredLoss, 1215-1276 AbsLoss, 1346-1363 AggregateLoss) -------------------------
+ * p prediction, t target of the same sizes, d = t - p, EPS = 1e-5, n_tot = elements of p.
+ * masked = |t + 666| <= 1e-8 + 666e-5 (T.isclose(t, -666.0) with Theano's rtol = 1e-5, atol = 1e-8;
+ * NaN is not masked); n_lab = unmasked elements.  The reference multiplies an element-wise array
+ * by n_tot / (n_lab + 1) and AggregateLoss takes its mean: n_tot cancels, the array is never made.
+ *
+ *   kind        element loss l (unmasked elements)                 term value L
+ *   SQUARED     0.5 d^2 g c,  g = [|d| >= margin] (1 without),     S1 / (n_lab + 1) - margin S2 / n_tot
+ *               c = sc / (|t| + sc) (1 without)                    S1 = sum l, S2 = sum c; second part
+ *   ABS         |d| g c,      c = sc |t| + 1                       only with a margin (loss.py:1084-1085)
+ *   BINARY_NLL  -xlogy0(t, p + EPS) - xlogy0(1 - t, 1 - p + EPS)   S1 / (n_lab + 1)
+ *               [- xlogy0(t, t + EPS) - xlogy0(1 - t, 1 - t + EPS) with subtract_label_entropy]
+ *               xlogy0(x, y) = 0 where x == 0, else x log y
+ *   GAUSS_NLL   0.5 log(2 pi) + log s + 0.5 ((t - mu) / s)^2       S1 / n_tot  (no mask)
+ *               s = exp(sig), log s = sig with sig_is_log
+ *
+ *   dL/dp: SQUARED -d g c / (n_lab + 1);  ABS -sgn(d) g c / (n_lab + 1), sgn 0 = 0;
+ *          BINARY_NLL (-t / (p + EPS) + (1 - t) / (1 - p + EPS)) / (n_lab + 1);  0 where masked;
+ *          GAUSS_NLL dmu = -(t - mu) / s^2 / n_tot, dsig = (1 / s - (t - mu)^2 / s^3) / n_tot, or
+ *          (1 - (t - mu)^2 / s^2) / n_tot with sig_is_log.
+ *   total = (1 / K) sum_k w_k L_k over the K terms of a mix (loss.py:1357-1363).
+ *
+ * margin / scale_correction / the mixing weights / coef are DEVICE scalars read when the kernels
+ * run: a captured launch follows later changes.  All arithmetic is f32 (sums of the mix: double). */
+enum { E2_LOSS_SQUARED = 0, E2_LOSS_ABS, E2_LOSS_BINARY_NLL, E2_LOSS_GAUSS_NLL };
+#define E2_MAX_LOSS_TERMS 8
+typedef struct e2_loss_term {
+  int kind;
+  const float* margin;            /* device scalar; NULL: none   (SQUARED / ABS)        */
+  const float* scale_correction;  /* device scalar; NULL: none   (SQUARED / ABS)        */
+  int subtract_label_entropy;     /* BINARY_NLL */
+  int sig_is_log;                 /* GAUSS_NLL  */
+} e2_loss_term;
+/* rows of 4 floats that e2_loss_fwd writes for a prediction of these sizes (one per work-group,
+ * at most 1024); depends on the sizes alone.  0: empty / null view */
+size_t e2_loss_partials(e2_ctx*, const e2_tensor5* pred);
+/* forward sums of one term: partials[row] = (S1, n_lab, S2, 0) of the row's work-group, every row
+ * written by a plain store (no zero fill needed, no atomics); partials 16-byte aligned.  sig: the
+ * GAUSS_NLL sigma view, NULL otherwise.  (loss.py:877-885, 994-1009, 1075-1094, 1256-1273) */
+int e2_loss_fwd(e2_ctx*, const e2_loss_term*, const e2_tensor5* pred, const e2_tensor5* sig,
+                const e2_tensor5* target, float* partials);
+/* one small launch for k <= E2_MAX_LOSS_TERMS terms: sums each slab in a fixed order (bit-
+ * reproducible) and writes term_loss[j] = L_j, count[j] = n_lab_j (n_tot_j for GAUSS_NLL),
+ * coef[j] = mix[j] / (k (n_lab_j + 1)) (GAUSS_NLL: mix[j] / (k n_tot_j)) and loss_out[0] = total.
+ * terms / partials / rows / n_tot are HOST arrays of k entries; mix, coef, term_loss, count
+ * (k floats each) and loss_out are device memory.  (loss.py:1357-1363) */
+int e2_loss_mix(e2_ctx*, int k, const e2_loss_term* terms, float* const* partials,
+                const size_t* rows, const int64_t* n_tot, const float* mix, float* coef,
+                float* term_loss, float* count, float* loss_out);
+/* gradient of the mixed total wrt pred (and sig): dpred (=|+=) coef[0] * d(sum l)/dp, accumulate
+ * != 0 adds to what the view holds.  coef: the DEVICE scalar e2_loss_mix wrote for this term.
+ * dpred or dsig may be NULL (not wanted), not both; dsig is for GAUSS_NLL alone.  Nothing outside
+ * the views is written.  (T.grad of the lines above) */
+int e2_loss_bwd(e2_ctx*, const e2_loss_term*, const e2_tensor5* pred, const e2_tensor5* sig,
+                const e2_tensor5* target, const float* coef, const e2_tensor5* dpred,
+                const e2_tensor5* dsig, int accumulate);
+
 #ifdef __cplusplus
 }
 #endif
