@@ -165,6 +165,8 @@ def _load():
         "e2_transpose_ncdhw_to_ndhwc": (C.c_int, [vp, P5, fp]),
         "e2_transpose_ndhwc_to_ncdhw": (C.c_int, [vp, fp, P5]),
         "e2_copy5": (C.c_int, [vp, P5, P5, i]),
+        "e2_set_dgrad_zinset": (C.c_int, [vp, i]),
+        "e2_pad5": (C.c_int, [vp, P5, P5, i, i, i, C.c_float, i]),
         "e2_fill": (C.c_int, [vp, fp, sz, C.c_float]),
         "e2_softmax_nll_fwd": (C.c_int, [vp, P5, P5, P5, fp]),
         "e2_softmax_nll_bwd": (C.c_int, [vp, P5, P5, fp, P5, fp]),
@@ -755,6 +757,18 @@ class Context:
     def copy5(self, src, dst, accumulate=False):
         _chk(_lib.e2_copy5(self.h, C.byref(t5(src)), C.byref(t5(dst)), int(accumulate)),
              "e2_copy5")
+
+    def set_dgrad_zinset(self, planes):
+        """the dgrad launches that follow read a padded gradient inset by ``planes`` z planes on
+        either side (e2_set_dgrad_zinset); 0 withdraws it"""
+        _chk(_lib.e2_set_dgrad_zinset(self.h, int(planes)), "e2_set_dgrad_zinset")
+
+    def pad5(self, src, dst, pad, value=0.0, frame_only=False):
+        """dst = src inside a frame of ``value`` of widths ``pad`` = (pz, px, py) on the three
+        spatial axes (e2_pad5); ``frame_only``: the interior of dst is left alone (src may be None)"""
+        _chk(_lib.e2_pad5(self.h, C.byref(t5(src)) if src is not None else None, C.byref(t5(dst)),
+                          int(pad[0]), int(pad[1]), int(pad[2]), float(value), int(bool(frame_only))),
+             "e2_pad5")
 
     def fill(self, t, value=0.0):
         if not t.is_contiguous():

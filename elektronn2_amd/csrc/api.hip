@@ -51,6 +51,7 @@ extern "C" int e2_ctx_create(int device, e2_ctx** out) {
   c->loss_sum_mode = 0;
   c->loss_count_out = nullptr;
   c->input_slack = 0;
+  c->dgrad_zinset = 0;
   c->image_rows = 0;
   c->last_fill_ptr = nullptr;
   c->last_fill_n = 0;
@@ -88,6 +89,15 @@ extern "C" int e2_set_loss_grad_mode(e2_ctx* ctx, int sum_mode, float* count_out
 extern "C" int e2_set_input_slack(e2_ctx* ctx, int bytes) {
   E2_REQUIRE(ctx && bytes >= 0, "e2_set_input_slack: bad argument");
   ctx->input_slack = bytes;
+  return 0;
+}
+
+/* The data-gradient launches that follow read a padded gradient whose zero border has been cut
+ * by `planes` z planes on either side (a sub-view of the kd - 1 planes the buffer carries): they
+ * skip only the kd - 1 - planes border planes that are left.  0 (the default): the whole border. */
+extern "C" int e2_set_dgrad_zinset(e2_ctx* ctx, int planes) {
+  E2_REQUIRE(ctx && planes >= 0, "e2_set_dgrad_zinset: bad argument");
+  ctx->dgrad_zinset = planes;
   return 0;
 }
 
@@ -329,7 +339,9 @@ static int conv_dgrad_packed(e2_ctx* ctx, const e2_tensor5* dy_pad, const void* 
   a.osN = dx->sn; a.osC = dx->sc; a.osZ = dx->sd; a.osY = dx->sh;
   if (int rc = image_dims(ctx, cin, dy_pad->c, &a.ciP, &a.coP)) return rc;
   a.upz = a.upy = a.upx = 1;
-  a.zpad = kd - 1;
+  E2_REQUIRE(ctx->dgrad_zinset <= kd - 1, "conv3d_dgrad: z inset %d of a border of %d planes",
+             ctx->dgrad_zinset, kd - 1);
+  a.zpad = kd - 1 - ctx->dgrad_zinset;
   a.parts_max = max_parts; a.part_stride = part_stride; a.nparts = nparts;
   return e2i_igemm_conv(ctx, a);
 }
@@ -382,6 +394,8 @@ extern "C" int e2_conv3d_dgrad_packed_actbwd(e2_ctx* ctx, const e2_tensor5* dy_p
   a.osN = dx.sn; a.osC = dx.sc; a.osZ = dx.sd; a.osY = dx.sh;
   if (int rc = image_dims(ctx, cin, dy_pad->c, &a.ciP, &a.coP)) return rc;
   a.upz = a.upy = a.upx = 1;
+  // (e2_set_dgrad_zinset is NOT read here: this launch writes the parent's PADDED gradient and is
+  // only issued for a valid conv behind a valid conv -- Conv._actbwd_into_parent)
   a.zpad = kd - 1;
   int done = 0;
   if (o->sh == o->w) {                          // the epilogue reads dense mask rows

@@ -24,6 +24,7 @@ struct e2_ctx {
   float* loss_count_out;    // ... and the count is also written here (the slot behind the gradient arena)
   int input_slack;          // e2_set_input_slack: finite readable bytes behind the x of the launches that follow
   int image_rows;           // e2_set_image_rows: floats per k-row of the packed images the next launches read (0 = formula)
+  int dgrad_zinset;         // e2_set_dgrad_zinset: z planes cut off either side of the padded gradient the next dgrad launches read
   char last_launch[160];    // e2_last_launch: "<kernel family> <tiling that ran> <forced|model|fallback>"
   unsigned tiling_fallbacks;   // launches since e2_ctx_create whose forced tiling was NOT the one that ran
 };

@@ -46,9 +46,10 @@ def neuro3d(in_sh=(None, 1, 23, 185, 185), params=None, name=None, mfp=False):
     return _finish(nm, inp, out, name, mfp)
 
 
-def unet3d_lite(in_sh=(None, 1, 22, 140, 140), name=None):
+def unet3d_lite(in_sh=(None, 1, 22, 140, 140), name=None, conv_mode='valid'):
     """examples/unet3d_lite.py:59-118: three (1,2,2) poolings, two convs per level,
-    three UpConvMerge (crop + concat) stages, 2-class head."""
+    three UpConvMerge (crop + concat) stages, 2-class head.  ``conv_mode`` goes to every Conv
+    (neural.py:520-530): with 'same' the prediction has the patch's extent and no merge crops."""
     from . import neuromancer as nm
     if name is not None:
         nm.model_manager.newmodel(name)
@@ -56,20 +57,20 @@ def unet3d_lite(in_sh=(None, 1, 22, 140, 140), name=None):
     skips = []
     out = inp
     for n_f in (32, 64, 128):                      # contracting path
-        out = nm.Conv(out, n_f, (1, 3, 3))
-        out = nm.Conv(out, n_f, (1, 3, 3))
+        out = nm.Conv(out, n_f, (1, 3, 3), conv_mode=conv_mode)
+        out = nm.Conv(out, n_f, (1, 3, 3), conv_mode=conv_mode)
         skips.append(out)
         out = nm.Pool(out, (1, 2, 2), mode='max')
-    out = nm.Conv(out, 256, (3, 3, 3))
-    out = nm.Conv(out, 256, (3, 3, 3))
+    out = nm.Conv(out, 256, (3, 3, 3), conv_mode=conv_mode)
+    out = nm.Conv(out, 256, (3, 3, 3), conv_mode=conv_mode)
     for skip, up_f, n_f, k in ((skips[2], 512, 256, (1, 3, 3)),   # expanding path
                                (skips[1], 256, 128, (3, 3, 3)),
                                (skips[0], 128, 64, (3, 3, 3))):
         out = nm.UpConvMerge(skip, out, up_f)
-        out = nm.Conv(out, n_f, k)
-        out = nm.Conv(out, n_f, k)
+        out = nm.Conv(out, n_f, k, conv_mode=conv_mode)
+        out = nm.Conv(out, n_f, k, conv_mode=conv_mode)
     feat = out
-    barr = nm.Conv(feat, 2, (1, 1, 1), activation_func='lin', name='barr')
+    barr = nm.Conv(feat, 2, (1, 1, 1), activation_func='lin', name='barr', conv_mode=conv_mode)
     probs = nm.Softmax(barr)
     target = nm.Input_like(feat, override_f=1, name='target')
     loss_pix = nm.MultinoulliNLL(probs, target, target_is_sparse=True, name='nll_barr')
@@ -81,35 +82,35 @@ def unet3d_lite(in_sh=(None, 1, 22, 140, 140), name=None):
     return model
 
 
-def unet3d(in_sh=(None, 1, 116, 132, 132), name=None):
+def unet3d(in_sh=(None, 1, 116, 132, 132), name=None, conv_mode='valid'):
     """examples/unet3d.py:61-100 (BASELINE configs[4]): three (2,2,2) poolings, two
     (3,3,3) convs per level, three UpConvMerge stages with UpConv p=(2,2,2), 2-class head;
-    (1,1,116,132,132) -> (1,2,28,44,44)."""
+    (1,1,116,132,132) -> (1,2,28,44,44).  ``conv_mode`` goes to every Conv."""
     from . import neuromancer as nm
     if name is not None:
         nm.model_manager.newmodel(name)
     inp = nm.Input(in_sh, 'b,f,z,x,y', name='raw')
-    conv0 = nm.Conv(inp, 32, (3, 3, 3))
-    conv1 = nm.Conv(conv0, 64, (3, 3, 3))
+    conv0 = nm.Conv(inp, 32, (3, 3, 3), conv_mode=conv_mode)
+    conv1 = nm.Conv(conv0, 64, (3, 3, 3), conv_mode=conv_mode)
     down0 = nm.Pool(conv1, (2, 2, 2), mode='max')
-    conv2 = nm.Conv(down0, 64, (3, 3, 3))
-    conv3 = nm.Conv(conv2, 128, (3, 3, 3))
+    conv2 = nm.Conv(down0, 64, (3, 3, 3), conv_mode=conv_mode)
+    conv3 = nm.Conv(conv2, 128, (3, 3, 3), conv_mode=conv_mode)
     down1 = nm.Pool(conv3, (2, 2, 2), mode='max')
-    conv4 = nm.Conv(down1, 128, (3, 3, 3))
-    conv5 = nm.Conv(conv4, 256, (3, 3, 3))
+    conv4 = nm.Conv(down1, 128, (3, 3, 3), conv_mode=conv_mode)
+    conv5 = nm.Conv(conv4, 256, (3, 3, 3), conv_mode=conv_mode)
     down2 = nm.Pool(conv5, (2, 2, 2), mode='max')
-    conv6 = nm.Conv(down2, 256, (3, 3, 3))
-    conv7 = nm.Conv(conv6, 512, (3, 3, 3))
+    conv6 = nm.Conv(down2, 256, (3, 3, 3), conv_mode=conv_mode)
+    conv7 = nm.Conv(conv6, 512, (3, 3, 3), conv_mode=conv_mode)
     mrg0 = nm.UpConvMerge(conv5, conv7, 512)
-    mconv0 = nm.Conv(mrg0, 256, (3, 3, 3))
-    mconv1 = nm.Conv(mconv0, 256, (3, 3, 3))
+    mconv0 = nm.Conv(mrg0, 256, (3, 3, 3), conv_mode=conv_mode)
+    mconv1 = nm.Conv(mconv0, 256, (3, 3, 3), conv_mode=conv_mode)
     mrg1 = nm.UpConvMerge(conv3, mconv1, 256)
-    mconv2 = nm.Conv(mrg1, 128, (3, 3, 3))
-    mconv3 = nm.Conv(mconv2, 128, (3, 3, 3))
+    mconv2 = nm.Conv(mrg1, 128, (3, 3, 3), conv_mode=conv_mode)
+    mconv3 = nm.Conv(mconv2, 128, (3, 3, 3), conv_mode=conv_mode)
     mrg2 = nm.UpConvMerge(conv1, mconv3, 128)
-    mconv4 = nm.Conv(mrg2, 64, (3, 3, 3))
-    mconv5 = nm.Conv(mconv4, 64, (3, 3, 3))
-    barr = nm.Conv(mconv5, 2, (1, 1, 1), activation_func='lin', name='barr')
+    mconv4 = nm.Conv(mrg2, 64, (3, 3, 3), conv_mode=conv_mode)
+    mconv5 = nm.Conv(mconv4, 64, (3, 3, 3), conv_mode=conv_mode)
+    barr = nm.Conv(mconv5, 2, (1, 1, 1), activation_func='lin', name='barr', conv_mode=conv_mode)
     probs = nm.Softmax(barr)
     target = nm.Input_like(mconv5, override_f=1, name='target')
     loss_pix = nm.MultinoulliNLL(probs, target, target_is_sparse=True, name='nll_barr')

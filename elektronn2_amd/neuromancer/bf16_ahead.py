@@ -44,6 +44,7 @@ def eligible(plan, node):
     fused head or the tail), without batch normalisation / MFP, relu or lin"""
     return (not node._fused_first(plan) and node._fused_head(plan) is None
             and node._tail(plan) is None and not node._bn() and not node._mfp_pool()
+            and node._valid_mode()       # ('same' / 'full' read a framed image of their own)
             and node.activation_func in ('relu', 'lin')
             and tuple(node._p3) in node._PART_WINDOWS)
 

@@ -613,9 +613,23 @@ def kernel_lists_from_node_descr(nodes):
     (model.py:870-895; UpConv excluded, as there)."""
     filters, pools, mfps = [], [], []
     for name, cls, args, kwargs in nodes:
+        if cls == 'Pad':
+            # grows every axis by 2 * pad: a "filter" of extent 1 - 2 * pad (neural.py:1259-1271)
+            pd = _dec_plain(args[1]) if len(args) > 1 else _dec_plain(kwargs['pad'])
+            filters.append(tuple(1 - 2 * int(v) for v in pd))
+            pools.append(tuple(1 for _ in pd))
+            mfps.append(False)
+            continue
         if cls != 'Conv':
             continue
         f = _dec_plain(args[2]) if len(args) > 2 else _dec_plain(kwargs['filter_shape'])
+        # border modes (neural.py:731-737): a 'same' conv keeps the extent -- effective filter
+        # extent 1; a 'full' conv grows it by f - 1 -- effective extent 2 - f
+        mode = args[4] if len(args) > 4 else kwargs.get('conv_mode', 'valid')
+        if mode == 'same':
+            f = tuple(1 for _ in f)
+        elif mode == 'full':
+            f = tuple(2 - int(v) for v in f)
         if len(args) > 3:
             p = _dec_plain(args[3])
         else:

@@ -5,6 +5,7 @@ bookkeeping (elektronn2/neuromancer/neural.py), executing through libe2hip.so.
   Conv      neural.py:500-859   conv -> max-pool -> +bias -> act   (F3 order)
   UpConv    neural.py:907-1129  F2 closed form, identity_init
   Crop      neural.py:1132-1190 zero-copy view
+  Pad       neural.py:1195-1279 constant frame (csrc/pad.hip)
   AutoMerge neural.py:1282-1407 (= UpConvMerge)
   Pool      neural.py:1409-1559
 
@@ -31,9 +32,19 @@ the 'lin' backward.  It keeps off every route that does not leave the pre-activa
 hard-wires relu (fused first layer, fused epilogue, tail, activation backward inside a consumer's
 launch, split-K slabs, bf16 operands made ahead); NeuralLayer._plain_act() is the one predicate.
 
+Border modes (``conv_mode=`` of Conv, neural.py:520-530,731-737; computations.py:287-291,
+320-326): 'same' and 'full' are the valid conv of the zero-framed input, frame f // 2 or f - 1
+per axis.  Such a node owns a framed image that every one of its GEMM launches reads as x: filled
+by one e2_pad5 launch per step, or -- where the parent's producing launch writes a strided view
+(Plan._inplace_frame) -- the parent's output IS the interior of that image and no launch runs.
+Its data gradient is the existing launch on the sub-view of the padded output gradient inset by
+the frame, which writes the parent's unpadded gradient.  Conv._valid_mode() is the one predicate
+that keeps such a node off the routes tied to a neighbour's geometry.  MFP and dense tiled
+prediction of such nets are rejected (prediction-time rewrites of valid nets).
+
 Outside the hot path and therefore rejected with NotImplementedError here:
 gradnet, batch_normalisation='fadeout', the activations 'prelu', 'maxout <i>', 'concentration'
-and 'radius', conv modes other than 'valid', 1-D convolutions.
+and 'radius', 1-D convolutions.
 """
 from __future__ import annotations
 
@@ -49,7 +60,7 @@ from .variables import VariableWeight, ConstantParam, VariableParam
 
 logger = logging.getLogger('elektronn2log')
 
-__all__ = ['Conv', 'UpConv', 'Pool', 'Crop', 'AutoMerge', 'UpConvMerge', 'NeuralLayer',
+__all__ = ['Conv', 'UpConv', 'Pool', 'Crop', 'Pad', 'AutoMerge', 'UpConvMerge', 'NeuralLayer',
            'FragmentsToDense', 'Perceptron']
 
 # fused into the pooling kernels / GEMM epilogues; and those that run through csrc/act.hip
@@ -291,9 +302,22 @@ class Conv(NeuralLayer):
             raise NotImplementedError("Cannot convolve non-standard shapes / axis orders. "
                                       "Implement reshaping before conv and "
                                       "re-reshaping after!")
-        if conv_mode != 'valid':
-            raise NotImplementedError("conv_mode=%r: only 'valid' is on the HIP hot path"
-                                      % (conv_mode,))
+        # border modes (neural.py:520-530,731-737; computations.py:287-291,320-326)
+        if conv_mode not in ('valid', 'same', 'full'):
+            raise ValueError("conv_mode must be 'valid', 'same' or 'full', not %r" % (conv_mode,))
+        if conv_mode == 'same' and any(int(f) % 2 == 0 for f in filter_shape):
+            raise ValueError('For "same"-mode convolution, filter shapes must be odd in all '
+                             'dimensions.')
+        # a filter of extent 1 on every axis has no border: any mode is the valid conv (and keeps
+        # the head / tail / 1x1x1 routes)
+        self._mode = 'valid' if all(int(f) == 1 for f in filter_shape) else conv_mode
+        if self._mode != 'valid' and np.asarray(parent.shape.mfp_offsets).shape[0] > 1:
+            # (a zero frame around each fragment is not the dense conv's border)
+            raise NotImplementedError("conv_mode=%r behind a max-fragment-pooling layer: MFP is a "
+                                      "prediction-time rewrite of valid nets only" % (conv_mode,))
+        if mfp and self._mode != 'valid':
+            raise NotImplementedError("mfp=True with conv_mode=%r: max-fragment pooling is a "
+                                      "prediction-time rewrite of valid nets only" % (conv_mode,))
         check_activation(activation_func)
         self.conv_dim = conv_dim
         self.w_sh = w_sh
@@ -321,7 +345,7 @@ class Conv(NeuralLayer):
         sh = self.parent.shape
         for j, (i, f, p) in enumerate(zip(self.spatial_axes, self.filter_shape,
                                           self.pool_shape)):
-            k = 1 - f
+            k = self._border(f)
             s = (sh[i] + k) // p
             if self.mfp:
                 if (sh[i] + k - p + 1) % p != 0:
@@ -349,11 +373,18 @@ class Conv(NeuralLayer):
         sh = sh.updateshape('f', self.n_f)
         self.shape = sh
 
+    def _border(self, f):
+        """output extent minus input extent of one axis with filter extent f (neural.py:731-737)"""
+        mode = self._mode
+        return {'valid': 1 - f, 'same': 0, 'full': f - 1}[mode]
+
     def _calc_comp_cost(self):
+        """neural.py:767-778: every mode but 'valid' counts s + f - 1 positions -- for 'same'
+        too, which computes s of them; the reference's quirk is kept so that costs compare."""
         sh = self.parent.shape
         n_position = 1
         for i, f, p in zip(self.spatial_axes, self.filter_shape, self.pool_shape):
-            n_position *= sh[i] + 1 - f
+            n_position *= sh[i] + (1 - f if self.conv_mode == 'valid' else f - 1)
         b = 1 if sh['b'] is None else sh['b']
         self.computational_cost = int(np.prod(self.w_sh)) * n_position * b
 
@@ -362,6 +393,8 @@ class Conv(NeuralLayer):
         s += "  n_f=%i, " % (self.n_f,)
         s += "%id conv, kernel=%s, pool=%s, " % (self.conv_dim, self.filter_shape,
                                                   self.pool_shape)
+        if self.conv_mode != 'valid':
+            s += "mode='%s', " % (self.conv_mode,)
         s += "act='%s', " % (self.activation_func,)
         return s
 
@@ -399,6 +432,34 @@ class Conv(NeuralLayer):
 
     def _bn(self):
         return self.batch_normalisation in ('train', 'predict')
+
+    # ---- border modes: the valid conv of the zero-framed input (computations.py:287-291,320-326)
+    def _valid_mode(self):
+        """'valid', or a mode that is the valid conv (all filter extents 1).  A node of another
+        mode reads a framed copy of its input and wants its data gradient on the interior alone:
+        it stays off every route that takes the geometry of a neighbour for granted (bf16 operand
+        images made ahead by the producer, activation backward inside a consumer's or the tail's
+        launch)."""
+        return self._mode == 'valid'
+
+    @property
+    def _q3(self):
+        """width of the zero frame per device axis: f // 2 ('same'), f - 1 ('full'), 0 ('valid')"""
+        m = self._mode
+        if m == 'valid':
+            return (0, 0, 0)
+        return tuple((k // 2 if m == 'same' else k - 1) for k in self._k3)
+
+    def _x(self, plan):
+        """what the node's GEMM launches read: the parent's output, or the framed image of it"""
+        xf = plan.scratch.get((self, 'xf'))
+        return plan.out[self.parent] if xf is None else xf
+
+    def _x_shape(self, plan):
+        """device shape of that tensor"""
+        sh = plan.out_shape(self.parent)
+        q = self._q3
+        return tuple(sh[:2]) + tuple(sh[2 + i] + 2 * q[i] for i in range(3))
 
     def _fused_first(self, plan):
         """Cin = 1 first layer with a supported kernel/pool: fused conv+pool+bias+act
@@ -481,6 +542,7 @@ class Conv(NeuralLayer):
             # of its two gradient GEMMs (bf16_ahead.py) -- the tail hands it the plain gradient
             return None
         if not (plan.opt['tail_gm'] and type(par) is Conv and not par._bn()
+                and par._valid_mode()
                 and par.dropout_rate is None     # (its output gradient has to exist to be gated)
                 and all(p == 1 for p in par._p3) and par.activation_func in ('relu', 'lin')
                 and (par, 'dy') in plan.scratch and not par._fused_first(plan)
@@ -531,6 +593,9 @@ class Conv(NeuralLayer):
         N = plan.out_shape(self.parent)[0]     # (the fragments of MFP sit on the batch axis)
         psp = self._sp3(self.parent.shape)
         k = self._k3
+        if not self._valid_mode():
+            plan.framed_input(self)            # (scratch 'xf': every launch below reads it as x)
+            psp = self._x_shape(plan)[2:]
         if self.mfp and plan.training:
             raise NotImplementedError("MFP is a prediction-time rewrite of the net "
                                       "(neural.py:531-533); train without it")
@@ -623,7 +688,7 @@ class Conv(NeuralLayer):
 
     # ---- the tuning keys of the node's three GEMM launches --------------------------------
     def _sig_fwd(self, plan):
-        x = plan.out[self.parent]
+        x = self._x(plan)
         cin = self.parent.shape['f']
         if self._fused_act(plan):
             return (2, self.n_f, cin) + tuple(self._k3) + tuple(plan.out[self].shape[2:]) + (x.stride(3),)
@@ -634,8 +699,20 @@ class Conv(NeuralLayer):
         return (1, self.parent.shape['f'], self.n_f) + tuple(self._k3) + tuple(dst.shape[2:]) + \
             (plan.scratch[self, 'dy_pad'].stride(3),)
 
+    def _dy_inset(self, plan):
+        """the padded output gradient as the data-gradient launch reads it: the whole of it for a
+        valid conv; inset by the frame width on every side for 'same' / 'full' (for 'full' that is
+        `dy` itself), so that the launch writes the parent's unpadded gradient and nothing is
+        computed for the frame"""
+        dyp = plan.scratch[self, 'dy_pad']
+        q = self._q3
+        if not any(q):
+            return dyp
+        D, H, W = dyp.shape[2:]
+        return dyp[:, :, q[0]:D - q[0], q[1]:H - q[1], q[2]:W - q[2]]
+
     def _sig_wgrad(self, plan):
-        x, dy = plan.out[self.parent], plan.scratch[self, 'dy']
+        x, dy = self._x(plan), plan.scratch[self, 'dy']
         return (self.n_f, self.parent.shape['f']) + tuple(self._k3) + tuple(dy.shape[2:]) + \
             (x.stride(3), dy.stride(3))
 
@@ -669,7 +746,11 @@ class Conv(NeuralLayer):
         ctx = plan.ctx
         if self._fused_head(plan) is not None:
             return                            # done by the Softmax / NLL node
-        x = plan.out[self.parent]
+        x = self._x(plan)
+        if plan.scratch.get((self, 'xf_launch')):
+            # the framed image by one launch (the in-place route has none: the parent's producing
+            # launch wrote the interior, the frame is zero since the plan was built)
+            ctx.pad5(plan.out[self.parent], x, self._q3)
         if self._fused_first(plan):
             nx = bf16_ahead.next_image(plan, self)
             if nx is not None:            # bf16 mode: + the next conv's channels-last input image
@@ -784,7 +865,7 @@ class Conv(NeuralLayer):
         ctx = plan.ctx
         if self._fused_head(plan) is not None:
             return
-        x = plan.out[self.parent]
+        x = self._x(plan)
         if self._fused_first(plan):
             if plan.opt['side_join_first']:
                 # (the last launch of the backward chain: next to the side stream's weight
@@ -941,27 +1022,39 @@ class Conv(NeuralLayer):
             got = [1]
             sig = (1, cin, self.n_f) + tuple(self._k3) + tuple(out.shape[2:]) + \
                 (dyp.stride(3),)
+            dyi = self._dy_inset(plan)         # ('same' / 'full': the interior's gradient only)
+            zin = self._q3[0]
+
             def dgrad():
+                if zin:                        # (the z border the launch may skip is thinner)
+                    ctx.set_dgrad_zinset(zin)
+                try:
+                    dgrad_launch()
+                finally:
+                    if zin:
+                        ctx.set_dgrad_zinset(0)
+
+            def dgrad_launch():
                 if ctx.bf16_memory_form():
                     ad = plan.bf16a.get((self, 'dgrad'))
                     if ad is not None and plan._dy_ready.get(self) and ad['tile'] == ctx.current_tiling('igemm'):
                         plan.ensure_wb()
-                        ctx.conv3d_dgrad_bf16_ex(dyp, self._w5(plan.param(self.w)), out,
+                        ctx.conv3d_dgrad_bf16_ex(dyi, self._w5(plan.param(self.w)), out,
                                                  ws=plan.bf16_ws(self), dy_cl=ad['cl'],
                                                  wb=ad['wb'] if plan._wb_ready else None)
                     else:
                         self._need_f32_dy(plan)
-                        ctx.conv3d_dgrad_bf16(dyp, self._w5(plan.param(self.w)), out,
+                        ctx.conv3d_dgrad_bf16(dyi, self._w5(plan.param(self.w)), out,
                                               ws=plan.bf16_ws(self))
                     got[0] = 1
                 elif gparts is not None:
                     self._need_f32_dy(plan)
                     with plan.image(wp):
-                        got[0] = ctx.conv3d_dgrad_packed_parts(dyp, wp, cin, self._k3, gparts)
+                        got[0] = ctx.conv3d_dgrad_packed_parts(dyi, wp, cin, self._k3, gparts)
                 else:
                     self._need_f32_dy(plan)
                     with plan.image(wp):
-                        ctx.conv3d_dgrad_packed(dyp, wp, cin, self._k3, out)
+                        ctx.conv3d_dgrad_packed(dyi, wp, cin, self._k3, out)
             plan.tuned('igemm', sig,
                        autotune.igemm_candidates(cin, self.n_f, self._k3, out.shape[2:]) +
                        plan.bf16_cands(self.n_f), dgrad, out=out)
@@ -976,6 +1069,7 @@ class Conv(NeuralLayer):
         from this node alone"""
         par = self.parent
         if not (plan.fuse_actbwd and type(par) is Conv and type(self) is Conv
+                and self._valid_mode() and par._valid_mode()
                 and par.dropout_rate is None     # (its output gradient has to exist to be gated)
                 and not par._bn() and all(p == 1 for p in par._p3)
                 and par.activation_func in ('relu', 'lin')
@@ -1323,6 +1417,51 @@ class Crop(Node):
 
     def _plan_bwd(self, plan):
         plan.add_grad_region(self.parent, self._slicer(), plan.grad[self])
+
+
+class Pad(Node):
+    """Pads the spatial axes of its parent's output with ``value`` (neural.py:1195-1279):
+    ``pad`` entries on either side of the three spatial axes.  Strides and fov are the parent's
+    (neural.py:1259-1271), the cost is 0 (neural.py:1273-1279).  An entry of 0 pads nothing on
+    that axis (the reference's ``pz:-pz`` slice is empty there; here it is accepted).  Device
+    side: one e2_pad5 launch (csrc/pad.hip); the backward is e2_copy5 from the interior view
+    of the output gradient."""
+
+    def __init__(self, parent, pad, value=0.0, name='pad', print_repr=True):
+        super(Pad, self).__init__(parent, name, print_repr)
+        if list(parent.shape.tags) != ['b', 'f', 'z', 'x', 'y']:
+            raise NotImplementedError(
+                'Padding is currently only implemented for "b,f,z,x,y" axis order.'
+                '\nParent has axes {}'.format(list(parent.shape.tags)))
+        try:
+            ok = len(pad) == 3 and all(int(v) == v and int(v) >= 0 for v in pad)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("pad must be three non-negative ints (z, x, y), not %r" % (pad,))
+        self.pad = tuple(int(v) for v in pad)
+        self.value = float(value)
+
+    def _calc_shape(self):
+        sh = self.parent.shape.copy()
+        for k, i in enumerate(self.parent.shape.spatial_axes):
+            sh = sh.updateshape(i, self.parent.shape[i] + 2 * self.pad[k])
+        self.shape = sh
+
+    def _calc_comp_cost(self):
+        self.computational_cost = 0
+
+    def _slicer(self):
+        sl = [slice(None), slice(None)]
+        for k, i in enumerate(self.parent.shape.spatial_axes):
+            sl.append(slice(self.pad[k], self.pad[k] + int(self.parent.shape[i])))
+        return tuple(sl)
+
+    def _plan_fwd(self, plan):
+        plan.ctx.pad5(plan.out[self.parent], plan.out[self], self.pad, self.value)
+
+    def _plan_bwd(self, plan):
+        plan.add_grad(self.parent, plan.grad[self][self._slicer()])
 
 
 def AutoMerge(parent1, parent2, upconv_n_f=None, merge_mode='concat',

@@ -393,6 +393,13 @@ class Node(object, metaclass=MetaNode):
             raise NotImplementedError("predict_dense: the HIP hot path covers 3-d nets")
         if len(self.input_nodes) != 1:
             raise ValueError("predict_dense needs a node with exactly one input")
+        for n in self.all_parents.values():
+            # tiling with overlap = fov and stride-offset interleaving are rewrites of VALID nets
+            if type(n).__name__ == 'Pad' or (hasattr(n, '_valid_mode') and not n._valid_mode()):
+                raise NotImplementedError(
+                    "predict_dense: node %s (%s) pads its input: dense tiled prediction covers "
+                    "valid nets only" % (n.name, "Pad" if type(n).__name__ == 'Pad'
+                                         else "conv_mode=%r" % (n.conv_mode,)))
         offset = np.asarray(self.shape.offsets)
         if np.any(offset < 0):
             raise ValueError("Cannot predict dense because the CNN contains "

@@ -58,6 +58,10 @@ SPEC = {
     "tail_gm": ("E2_TAIL_GM", _b, True, "the tail launch carries its parent's activation backward"),
     "upconv_packed": ("E2_UPCONV_PACKED", _b, True, "UpConv weight images packed by the plan's one repack launch"),
     "concat_alias": ("E2_CONCAT_ALIAS", _b, True, "a concat hands channel slices to parents only it consumes"),
+    "pad_inplace": ("E2_PAD_INPLACE", _b, True,
+                    "a 'same' / 'full' conv finds its parent's output inside its zero-framed input image "
+                    "wherever the parent's producing launch writes a strided view (no pad launch); off: "
+                    "every such conv pads by one e2_pad5 launch per step"),
     "zero_in_update": ("E2_ZERO_IN_UPDATE", _b, True, "the optimiser launch clears the gradient arena (finding 38)"),
     "image_stride": ("E2_IMAGE_STRIDE", _b, True,
                      "once a conv launch's tiling is known its packed weight image gets rows as long as that "

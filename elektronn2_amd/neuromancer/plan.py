@@ -158,9 +158,62 @@ class Plan(object):
         return t.reshape(tuple(t.shape[:2]) + tuple(t.shape[5 - (n - 2):]))
 
     def alloc_out(self, node):
-        self.out[node] = self.empty(self.out_shape(node))
+        q = self._inplace_frame(node)
+        if q is None:
+            self.out[node] = self.empty(self.out_shape(node))
+        else:
+            # the output as the interior of the framed image its 'same' / 'full' consumers read:
+            # the node's producing launch writes the view, the frame is zero from here on (nothing
+            # ever writes it), no pad launch runs.  Other consumers read the interior view.
+            sh = self.out_shape(node)
+            buf = self.zeros(tuple(sh[:2]) + tuple(sh[2 + i] + 2 * q[i] for i in range(3)))
+            self.scratch[node, 'frame'] = (q, buf)
+            self.out[node] = buf[:, :, q[0]:q[0] + sh[2], q[1]:q[1] + sh[3], q[2]:q[2] + sh[4]]
         if self.training and self.needs_grad(node):
             self.alloc_grad(node)
+
+    def _padded_consumers(self, node):
+        """the 'same' / 'full' Conv nodes of this plan that read ``node``'s output"""
+        return [c for c in node.children.values()
+                if hasattr(c, '_valid_mode') and not c._valid_mode() and c.parent is node
+                and any(n is c for n in self.nodes)]
+
+    def _inplace_frame(self, node):
+        """frame widths (qz, qx, qy) if ``node``'s output can live inside the framed image of its
+        border-mode consumers, else None (they pad by launch).  It can where the launch that
+        produces the output writes any strided view -- Pool, UpConv, Concat, Add (copies, and the
+        UpConv slices a Concat hands out); a Conv on its pooling / activation pass (not the fused
+        epilogue, whose kernel wants dense output rows, nor the fused first layer, batch
+        normalisation or MFP) -- every such consumer wants the same frame, and the node is neither
+        an Input nor an output of the plan (whose buffers the caller sees)."""
+        if not self.opt['pad_inplace'] or node.is_source or any(o is node for o in self.outputs):
+            return None
+        cons = self._padded_consumers(node)
+        if not cons or len(set(tuple(c._q3) for c in cons)) != 1:
+            return None
+        kind = type(node).__name__
+        if kind == 'Conv':
+            if (node._bn() or node._mfp_pool() or node._fused_first(self)
+                    or node._fused_act(self)):
+                return None
+        elif kind not in ('Pool', 'UpConv', 'Concat', 'Add'):
+            return None
+        if any(type(c).__name__ == 'Perceptron' for c in node.children.values()):
+            return None                       # (reads its input as one dense matrix)
+        return tuple(cons[0]._q3)
+
+    def framed_input(self, node):
+        """scratch 'xf' of a 'same' / 'full' Conv: the zero-framed image of its parent's output --
+        the buffer the parent's output already lives in (alloc_out), or one of the node's own that
+        a pad launch fills every step (scratch 'xf_launch')"""
+        q = tuple(node._q3)
+        fr = self.scratch.get((node.parent, 'frame'))
+        if fr is not None and fr[0] == q and self.out.get(node.parent) is not None \
+                and self.out[node.parent].data_ptr() == fr[1][:, :, q[0]:, q[1]:, q[2]:].data_ptr():
+            self.scratch[node, 'xf'] = fr[1]
+            return
+        self.scratch[node, 'xf'] = self.zeros(node._x_shape(self))
+        self.scratch[node, 'xf_launch'] = True
 
     def alloc_grad(self, node):
         self.grad[node] = self.empty(self.out_shape(node))
@@ -217,7 +270,7 @@ class Plan(object):
             if type(n).__name__ != 'Conv' or not hasattr(n, '_k3') or n.parent is None:
                 continue
             try:
-                psh = self.out_shape(n.parent)
+                psh = n._x_shape(self)
                 need_w = max(need_w, self.ctx.wgrad_bf16_ws_bytes(psh, n.n_f, n._k3))
                 need_c = max(need_c, self.ctx.conv_bf16_ws_bytes(psh, n.n_f, n._k3))
             except Exception:
@@ -241,7 +294,7 @@ class Plan(object):
                 return None
             if self._capturing:
                 raise RuntimeError("bf16 kept-copy buffer must exist before capture")
-            need = self.ctx.conv_bf16_xkeep_bytes(self.out_shape(node.parent), node._k3)
+            need = self.ctx.conv_bf16_xkeep_bytes(node._x_shape(self), node._k3)
             buf = torch.zeros(need, dtype=torch.uint8, device=self.ctx.device)
             self.scratch[node, 'xb_keep'] = buf
         return buf
@@ -253,7 +306,7 @@ class Plan(object):
         """the scratch of csrc/wgrad_bf16.hip (bf16 copies of x and dy, the f32 sums): its own
         buffer, because the weight gradient runs on the side stream next to the data
         gradient that uses ``bf16_ws``; one for the plan, sized for the largest layer"""
-        need = self.ctx.wgrad_bf16_ws_bytes(self.out_shape(node.parent), node.n_f, node._k3)
+        need = self.ctx.wgrad_bf16_ws_bytes(node._x_shape(self), node.n_f, node._k3)
         ws = self.scratch.get('bf16_wgrad_ws')
         if ws is None or ws.numel() < need:
             if self._capturing:
@@ -267,7 +320,7 @@ class Plan(object):
     def bf16_ws(self, node):
         """ONE scratch buffer for the bf16 planes / filter rows of every conv of the plan (the
         launches are ordered on one stream), sized for the largest layer"""
-        need = self.ctx.conv_bf16_ws_bytes(self.out_shape(node.parent), node.n_f, node._k3)
+        need = self.ctx.conv_bf16_ws_bytes(node._x_shape(self), node.n_f, node._k3)
         ws = self.scratch.get('bf16_ws')
         if ws is None or ws.numel() < need:
             if self._capturing:

@@ -342,6 +342,16 @@ int e2_copy5(e2_ctx*, const e2_tensor5* src, const e2_tensor5* dst,
              int accumulate);
 int e2_fill(e2_ctx*, float* ptr, size_t n, float value);
 
+/* ---- constant padding (neural.py:1195-1279 Pad; computations.py:287-291,320-326: the 'same' /
+ *      'full' border modes of conv() are the valid conv of the zero-framed input) ---------------
+ * dst = src surrounded by a frame of `value`: pz planes, py rows and px columns on either side,
+ * dst sizes = src sizes + 2 (pz, py, px); both arbitrary views.  One launch, one pass; nothing
+ * outside the dst view is written.  frame_only != 0: only the frame is written, the interior of
+ * dst keeps its contents and src is not read (may be NULL).  The backward of the Pad node is
+ * e2_copy5 from the interior view of the output gradient. */
+int e2_pad5(e2_ctx*, const e2_tensor5* src, const e2_tensor5* dst, int pz, int py, int px,
+            float value, int frame_only);
+
 /* Batching the zero-fills of a captured step (no reference counterpart).  A split-K conv
  * launch (forward / data gradient with a small output) zero-fills its output and then
  * accumulates with atomics; each such fill is a ~5 us kernel.  A caller that replays the
@@ -374,6 +384,11 @@ int e2_step_prologue(e2_ctx*, const float* ring, int n_slots, size_t slot_floats
  * tiling "MT,NT,9,0,S", csrc/conv_pw_wgrad.hip */
 int e2_set_input_slack(e2_ctx*, int bytes);
 int e2_conv_last_zero_fill(const e2_ctx*, void** ptr, size_t* n);
+/* the e2_conv3d_dgrad_packed* launches that follow read a SUB-VIEW of a padded gradient that is
+ * inset by `planes` z planes on either side (the data gradient of a 'same' / 'full' conv is wanted
+ * on the interior of the framed input only, computations.py:287-291): of the kd - 1 zero planes
+ * they may skip, kd - 1 - planes are left.  0 (the default) withdraws it. */
+int e2_set_dgrad_zinset(e2_ctx*, int planes);
 
 /* ---- loss (computations.py:175-176 softmax; loss.py:261-347
  *      MultinoulliNLL(target_is_sparse); loss.py:1357-1363 AggregateLoss) - */
