@@ -32,6 +32,10 @@ class E2Error(RuntimeError):
     pass
 
 
+# E2_POOL_* of include/e2hip.h (0 stays free for max)
+POOL_MODE = {'avg': 1, 'sum': 2}
+
+
 class Tensor5(C.Structure):
     _fields_ = [("ptr", C.c_void_p),
                 ("n", C.c_int32), ("c", C.c_int32), ("d", C.c_int32),
@@ -156,6 +160,8 @@ def _load():
         "e2_pool_bias_act_bwd": (C.c_int, [vp, P5, P5, fp, i, i, i, i, P5, fp]),
         "e2_maxpool3d_fwd": (C.c_int, [vp, P5, i, i, i, P5]),
         "e2_maxpool3d_bwd": (C.c_int, [vp, P5, P5, i, i, i, P5, i]),
+        "e2_pool3d_lin_fwd": (C.c_int, [vp, P5, i, i, i, i, i, i, i, P5]),
+        "e2_pool3d_lin_bwd": (C.c_int, [vp, P5, i, i, i, i, i, i, i, P5, i]),
         "e2_upconv3d_workspace_bytes": (sz, [i, i, i, i, i, i, i, i, i]),
         "e2_upconv3d_fwd": (C.c_int, [vp, P5, fp, fp, i, i, i, i, i, P5, vp, sz]),
         "e2_upconv3d_bwd": (C.c_int, [vp, P5, fp, P5, P5, i, i, i, i, P5, fp, fp, vp, sz]),
@@ -698,6 +704,22 @@ class Context:
         _chk(_lib.e2_maxpool3d_bwd(self.h, C.byref(t5(dout)), C.byref(t5(x)), pool[0],
                                    pool[1], pool[2], C.byref(t5(dx)), int(accumulate)),
              "e2_maxpool3d_bwd")
+
+    def pool_lin_fwd(self, x, pool, stride, mode, out):
+        """out = average ('avg') / sum ('sum') of x over windows ``pool`` placed every ``stride``
+        (pad 0, extent floor((in - p) / s) + 1); any strided views"""
+        _chk(_lib.e2_pool3d_lin_fwd(self.h, C.byref(t5(x)), int(pool[0]), int(pool[1]),
+                                    int(pool[2]), int(stride[0]), int(stride[1]), int(stride[2]),
+                                    POOL_MODE.get(mode, mode), C.byref(t5(out))),
+             "e2_pool3d_lin_fwd")
+
+    def pool_lin_bwd(self, dout, pool, stride, mode, dx, accumulate=False):
+        """dx (+)= the gradient of pool_lin_fwd: a gather over the windows that hold each element;
+        elements no window holds become +0 (are left alone with ``accumulate``)"""
+        _chk(_lib.e2_pool3d_lin_bwd(self.h, C.byref(t5(dout)), int(pool[0]), int(pool[1]),
+                                    int(pool[2]), int(stride[0]), int(stride[1]), int(stride[2]),
+                                    POOL_MODE.get(mode, mode), C.byref(t5(dx)),
+                                    int(bool(accumulate))), "e2_pool3d_lin_bwd")
 
     # ---- upconv ------------------------------------------------------------------
     def upconv_ws_bytes(self, cout, cin, pool, x_shape):

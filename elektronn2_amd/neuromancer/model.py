@@ -766,6 +766,15 @@ def modelload(file_name, model=None, override_mfp_to_active=False, imposed_patch
             parents_of(by_name[nm_][3], acc)
             todo.extend(acc)
         for n in nodes:
+            if n[1] == 'Pool' and n[0] in keep:
+                # a Pool node is never fragment-pooled (the reference refuses mfp there,
+                # neural.py:1535-1537, and computations.fragmentpool knows no stride): with a
+                # linear mode the dense rewrite does not exist
+                mode = n[2][4] if len(n[2]) > 4 else n[3].get('mode', 'max')
+                if mode != 'max':
+                    raise NotImplementedError(
+                        "override_mfp_to_active: Pool node %r (mode %r) has no max-fragment-"
+                        "pooling form; use predict_dense" % (n[0], mode))
             if n[1] == 'Conv' and n[0] in keep:
                 n[3]['mfp'] = True
         dense_name = 'to_dense_' + pred[0]

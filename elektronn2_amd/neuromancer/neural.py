@@ -7,7 +7,7 @@ bookkeeping (elektronn2/neuromancer/neural.py), executing through libe2hip.so.
   Crop      neural.py:1132-1190 zero-copy view
   Pad       neural.py:1195-1279 constant frame (csrc/pad.hip)
   AutoMerge neural.py:1282-1407 (= UpConvMerge)
-  Pool      neural.py:1409-1559
+  Pool      neural.py:1409-1559 max (stride == pool); average / sum with any stride (csrc/pool.hip)
 
   Perceptron neural.py:258-410  dot product (+ batch norm) -> +bias -> act  (config 1)
 
@@ -41,6 +41,18 @@ Its data gradient is the existing launch on the sub-view of the padded output gr
 the frame, which writes the parent's unpadded gradient.  Conv._valid_mode() is the one predicate
 that keeps such a node off the routes tied to a neighbour's geometry.  MFP and dense tiled
 prediction of such nets are rejected (prediction-time rewrites of valid nets).
+
+Pooling (``Pool(parent, pool_shape, stride=None, mfp=False, mode='max')``, neural.py:1409-1559;
+computations.py:538-649): 'max' runs through the max-pool kernels with ``stride`` None or equal to
+``pool_shape``.  The linear modes -- 'average' (stored as 'average_inc_pad'), 'average_inc_pad',
+'average_exc_pad' (the same without padding) and 'sum' -- take any stride >= 1 per axis (overlapping
+windows below the pool extent, gaps above it) and run through e2_pool3d_lin_fwd / _bwd
+(csrc/pool.hip): one launch each way, the backward a gather that needs no atomics and does not read
+the input.  2-D parents ('b,f,x,y' / 'b,f,y,x') with a 2-tuple are the same launches with a unit z
+window, in every mode.  Rejected: 'max' with a stride of its own (NotImplementedError, as the
+reference off cuDNN), ``mfp=True``, 1-D parents, other axis orders, an unknown mode (ValueError that
+lists the modes); ``modelload(override_mfp_to_active=True)`` on a net whose prediction path holds a
+linear-mode Pool raises a NotImplementedError that names the node (there is no fragment form of it).
 
 Outside the hot path and therefore rejected with NotImplementedError here:
 gradnet, batch_normalisation='fadeout', the activations 'prelu', 'maxout <i>', 'concentration'
@@ -1512,7 +1524,23 @@ UpConvMerge = AutoMerge
 
 
 class Pool(Node):
-    """Max-pooling node (neural.py:1409-1559)."""
+    """Pooling node (neural.py:1409-1559).
+
+    ``mode``: 'max' (csrc/pointwise.hip, ``stride`` None or == ``pool_shape``), or one of the
+    linear modes 'average' (stored as 'average_inc_pad', neural.py:1454-1455), 'average_inc_pad',
+    'average_exc_pad' (no padding here: the same as inc_pad) and 'sum' (csrc/pool.hip).  The linear
+    modes take any ``stride`` >= 1 per axis: overlapping windows below the pool extent, gaps above
+    it.  3-D parents ('b,f,z,x,y') with a 3-tuple, 2-D parents ('b,f,x,y' / 'b,f,y,x') with a
+    2-tuple (the 3-D launches with a unit z window).
+
+    Rejected: ``mfp=True`` (as in the reference), 'max' with a stride of its own
+    (computations.py:612-613 off cuDNN), 1-D parents and other axis orders.  Under
+    ``modelload(override_mfp_to_active=True)`` a Pool node is never turned into fragment pooling
+    (the reference refuses ``mfp`` in Pool._calc_shape, and computations.fragmentpool has no
+    stride); for a linear-mode Pool on the prediction path modelload raises a NotImplementedError
+    that names the node, a max Pool is left as it always was."""
+
+    MODES = ('max', 'average', 'average_inc_pad', 'average_exc_pad', 'sum')
 
     def __init__(self, parent, pool_shape, stride=None, mfp=False, mode='max',
                  name="pool", print_repr=True):
@@ -1520,23 +1548,41 @@ class Pool(Node):
         if mfp:
             # the reference refuses it as well (neural.py:1535-1536, in _calc_shape)
             raise NotImplementedError("Check this first before use")
-        if stride is not None and tuple(stride) != tuple(pool_shape):
+        if mode not in self.MODES:
+            raise ValueError("Pooling mode %r: must be one of %s" % (mode, ", ".join(self.MODES)))
+        if mode == 'average':
+            mode = 'average_inc_pad'            # neural.py:1454-1455
+        if stride is None:
+            stride = pool_shape
+        if len(tuple(stride)) != len(tuple(pool_shape)):
+            raise ValueError("stride %s and pool_shape %s differ in length"
+                             % (tuple(stride), tuple(pool_shape)))
+        if mode == 'max' and tuple(stride) != tuple(pool_shape):
             raise NotImplementedError("Stride!=Pool using 3d pooling")   # computations.py:612
-        if mode != 'max':
-            raise NotImplementedError("Pooling mode %r needs cuDNN in the reference; "
-                                      "only 'max' is on the hot path" % (mode,))
         self.pool_shape = tuple(int(p) for p in pool_shape)
-        self.pool_stride = self.pool_shape
+        self.pool_stride = tuple(int(p) for p in stride)
+        if any(p < 1 for p in self.pool_shape) or any(p < 1 for p in self.pool_stride):
+            raise ValueError("pool_shape %s / stride %s: every entry must be >= 1"
+                             % (self.pool_shape, self.pool_stride))
         self.mfp = False
         self.mode = mode
         self.strides = parent.shape.strides
         self.axis = parent.shape.tag2index('f')
         spatial_axes = self.parent.shape.spatial_axes
-        if len(pool_shape) != 3 or len(self.parent.shape) != 5 or spatial_axes != [2, 3, 4]:
+        conv_dim, x_dim = len(self.pool_shape), len(self.parent.shape)
+        if not ((conv_dim == 3 and x_dim == 5 and spatial_axes == [2, 3, 4])
+                or (conv_dim == 2 and x_dim == 4 and spatial_axes == [2, 3])):
             raise NotImplementedError("Cannot pool non-standard shapes / axis orders "
                                       "on the HIP hot path.")
         self.spatial_axes = spatial_axes
-        self.conv_dim = 3
+        self.conv_dim = conv_dim
+        # the launches: (z, x, y) with a unit z window for 2-D parents (Plan.out_shape)
+        self._p3 = (1,) * (3 - conv_dim) + self.pool_shape
+        self._s3 = (1,) * (3 - conv_dim) + self.pool_stride
+
+    def _linear(self):
+        """'avg' / 'sum' for the modes of csrc/pool.hip, None for max"""
+        return {'max': None, 'sum': 'sum'}.get(self.mode, 'avg')
 
     def _make_output(self):
         self.output = Sym(self, floatX)
@@ -1557,11 +1603,20 @@ class Pool(Node):
         self.shape = sh.updatestrides(self.strides)
 
     def _plan_fwd(self, plan):
-        plan.ctx.maxpool3d_fwd(plan.out[self.parent], self.pool_shape, plan.out[self])
+        lin = self._linear()
+        if lin is None:
+            plan.ctx.maxpool3d_fwd(plan.out[self.parent], self._p3, plan.out[self])
+        else:
+            plan.ctx.pool_lin_fwd(plan.out[self.parent], self._p3, self._s3, lin, plan.out[self])
 
     def _plan_bwd(self, plan):
         if not plan.needs_grad(self.parent):
             return
         dst, first = plan.grad_slot(self.parent)
-        plan.ctx.maxpool3d_bwd(plan.grad[self], plan.out[self.parent], self.pool_shape, dst,
-                               accumulate=not first)
+        lin = self._linear()
+        if lin is None:
+            plan.ctx.maxpool3d_bwd(plan.grad[self], plan.out[self.parent], self._p3, dst,
+                                   accumulate=not first)
+        else:
+            plan.ctx.pool_lin_bwd(plan.grad[self], self._p3, self._s3, lin, dst,
+                                  accumulate=not first)

@@ -298,6 +298,23 @@ int e2_maxpool3d_bwd(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* x,
                      int pz, int py, int px, const e2_tensor5* dx,
                      int accumulate);
 
+/* ---- average / sum pooling with a stride of its own (computations.py:538-649 pooling(), the
+ *      dnn_pool route: modes 'average_inc_pad' / 'average_exc_pad' / 'sum', pad 0, any stride;
+ *      neural.py:1409-1559 Pool node) --------------------------------------------------------
+ * out = scale * (sum of x over the window (pz, py, px) at (oz sz, oy sy, ox sx)), walked in
+ * ascending (z, y, x) order in f32; scale = 1 (SUM) or 1 / (pz py px) (AVG; at pad 0 inc_pad and
+ * exc_pad coincide).  out sizes = floor((in - p) / s) + 1 per axis; windows may overlap (s < p) or
+ * leave gaps (s > p).  The backward is a gather over the windows that hold each element of dx:
+ * no atomics, the same bits every run; elements that no window holds are written as +0, or left
+ * as they are with accumulate != 0 (dx += gradient, a plain read-add-write).  x is not needed.
+ * All views arbitrary; nothing outside out / dx is written.  p < 1, s < 1, p > in, sizes that do
+ * not match, another mode and a channel of 2^31 elements or more are errors. */
+enum { E2_POOL_AVG = 1, E2_POOL_SUM = 2 };   /* 0 stays free for max */
+int e2_pool3d_lin_fwd(e2_ctx*, const e2_tensor5* x, int pz, int py, int px, int sz, int sy,
+                      int sx, int mode, const e2_tensor5* out);
+int e2_pool3d_lin_bwd(e2_ctx*, const e2_tensor5* dout, int pz, int py, int px, int sz, int sy,
+                      int sx, int mode, const e2_tensor5* dx, int accumulate);
+
 /* ---- UpConv  (neural.py:989-1072; computations.py:216-255 upconv(),
  *      749-782 unpooling_nd; F2: y[n,co,p*i+r] = sum_ci w[co,ci,r] x[n,ci,i]) */
 /* (n,d,h,w) = dims of the UpConv INPUT x. */
