@@ -178,6 +178,8 @@ def _load():
         "e2_softmax_nll_bwd": (C.c_int, [vp, P5, P5, fp, P5, fp]),
         "e2_softmax_nll_fwd_w": (C.c_int, [vp, P5, P5, P5, fp, PW]),
         "e2_softmax_nll_bwd_w": (C.c_int, [vp, P5, P5, fp, P5, fp, PW]),
+        "e2_softmax_nll_grouped_fwd": (C.c_int, [vp, P5, P5, P5, i, fp]),
+        "e2_softmax_nll_grouped_bwd": (C.c_int, [vp, P5, P5, i, fp, P5, fp]),
         "e2_head_fwd_w": (C.c_int, [vp, P5, fp, fp, i, P5, P5, fp, PW]),
         "e2_head_bwd_w": (C.c_int, [vp, P5, fp, P5, P5, fp, P5, i, fp, fp, fp, C.c_void_p,
                                     sz, PW]),
@@ -840,6 +842,18 @@ class Context:
             _chk(_lib.e2_softmax_nll_bwd(*args), "e2_softmax_nll_bwd")
         else:
             _chk(_lib.e2_softmax_nll_bwd_w(*(args + (C.byref(weights),))), "e2_softmax_nll_bwd_w")
+
+    def softmax_nll_grouped_fwd(self, logits, target, probs, n_indep, stats):
+        """``n_indep`` softmaxes over consecutive feature groups and their NLL in one launch;
+        ``target`` (n, n_indep, d, h, w) or None: probabilities only, ``stats`` is not touched"""
+        _chk(_lib.e2_softmax_nll_grouped_fwd(
+            self.h, C.byref(t5(logits)), C.byref(t5(target)) if target is not None else None,
+            C.byref(t5(probs)), int(n_indep), _fp(stats)), "e2_softmax_nll_grouped_fwd")
+
+    def softmax_nll_grouped_bwd(self, probs, target, n_indep, stats, dlogits, loss_out):
+        _chk(_lib.e2_softmax_nll_grouped_bwd(
+            self.h, C.byref(t5(probs)), C.byref(t5(target)), int(n_indep), _fp(stats),
+            C.byref(t5(dlogits)), _fp(loss_out)), "e2_softmax_nll_grouped_bwd")
 
     def fill_multi(self, ptrs_dev, counts_dev, n, value=0.0):
         """one launch that fills n flat regions (int64 device tensors of pointers / counts)"""

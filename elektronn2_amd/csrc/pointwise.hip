@@ -576,13 +576,13 @@ __global__ void ndhwc_to_ncdhw_kernel(const float* __restrict__ src, View5 dst) 
 // changed the instructions of the unweighted kernels).
 __global__ void softmax_nll_fwd_kernel(View5 lg, View5 tg, View5 pr,
                                        float* __restrict__ stats) {
-  constexpr bool WT = false;
+  constexpr bool WT = false, HAS_T = true;
   const NllW wt{};
 #include "softmax_nll_fwd_body.hpp"
 }
 __global__ void softmax_nll_fwd_w_kernel(View5 lg, View5 tg, View5 pr,
                                          float* __restrict__ stats, NllW wt) {
-  constexpr bool WT = true;
+  constexpr bool WT = true, HAS_T = true;
 #include "softmax_nll_fwd_body.hpp"
 }
 

@@ -1,5 +1,6 @@
-// body of softmax_nll_fwd_kernel / softmax_nll_fwd_w_kernel (pointwise.hip): in scope are the flag
-// WT, the kernel's arguments and `NllW wt`.
+// body of softmax_nll_fwd_kernel / softmax_nll_fwd_w_kernel (pointwise.hip) and of
+// softmax_nll_grouped_fwd_kernel (nll_grouped.hip): in scope are the flags WT and HAS_T (false:
+// no target, probabilities only), the kernel's arguments and `NllW wt`.
   __shared__ float red[4];
   const long S = (long)lg.d * lg.h * lg.w;
   const long s = blockIdx.x * 256L + threadIdx.x;
@@ -14,7 +15,7 @@
     for (int c = 1; c < lg.c; ++c) m = fmaxf(m, lp[c * lg.sc]);
     float den = 0.f;
     for (int c = 0; c < lg.c; ++c) den += expf(lp[c * lg.sc] - m);
-    const float tv = tg.p[vidx(tg, n, 0, z, y, x)];
+    const float tv = HAS_T ? tg.p[vidx(tg, n, 0, z, y, x)] : -1.f;
     float* pp = pr.p + vidx(pr, n, 0, z, y, x);
     float ev = 1.f;
     if constexpr (WT) {

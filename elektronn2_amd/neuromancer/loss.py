@@ -20,11 +20,21 @@ the fused tail (csrc/tail.hip), the fused head (csrc/head.hip) or the generic pa
 The weighted tail launch is f32 only: in bf16 mode (``set_mfma_dtype('bf16')``) a neuro3d-style net
 with a weighted loss needs the plan option ``bf16_tail`` off (the separate kernels then run; the
 choice of the path never depends on the weights, so the launch reports an error otherwise).
-Weak training, dense targets and several independent softmaxes under one MultinoulliNLL are
-outside the hot path and raise NotImplementedError.  ``Softmax(n_indep > 1)`` (independent softmaxes over
-consecutive feature groups, loss.py:82-92) exists for ``MalisNLL`` (loss.py:560-690,
-SURVEY.md 8f-4): forward and gradient on the device, the MALIS counts by the host C++
-of csrc/malis.cpp between the forward and the backward segment of the step.
+Weak training and dense targets are outside the hot path and raise NotImplementedError.
+
+``Softmax(n_indep = E > 1)`` (independent softmaxes over consecutive feature groups,
+loss.py:82-92) trains under ``MultinoulliNLL(..., target_is_sparse=True)`` with a target
+``(b, E, spatial...)`` -- what ``data.PatchSampler.getbatch(affinities='affinity')`` returns --
+(loss.py:275-285, 338-346):
+    loss = sum over the labelled (item, group, position) of -log(p_target + 1e-5)
+           / (n_labelled + 1e-5),      ONE count over all groups,
+one forward and one backward launch for all groups (csrc/nll_grouped.hip).  The fused head and
+tail step aside for such a softmax; class / example weights and the class masks with
+``n_indep > 1`` raise NotImplementedError (the reference broadcasts a length-n_class vector
+against E * n_class features).  ``Errors`` of such a net compares the argmax inside each group
+(loss.py:737-748).  The same Softmax also serves ``MalisNLL`` (loss.py:560-690):
+forward and gradient on the device, the MALIS counts by the host C++ of csrc/malis.cpp between
+the forward and the backward segment of the step.
 
 Element-wise losses (csrc/loss_elem.hip): ``SquaredLoss``, ``AbsLoss``, ``BinaryNLL``,
 ``GaussianNLL`` over any prediction node whose output the plan materialises (a Conv with any
@@ -136,9 +146,11 @@ class MultinoulliNLL(Node):
         if not isinstance(pred, Softmax):
             raise ValueError("The prob input to a MultinoulliNLL-node must be "
                              "a Softmax-Node.")
-        if pred.n_indep != 1:
-            raise NotImplementedError("MultinoulliNLL over n_indep > 1 is outside the "
-                                      "HIP hot path")
+        if pred.n_indep != 1 and (len(parents) > 2 or cw_param is not None):
+            # (the reference broadcasts a length-n_class vector against n_indep * n_class features)
+            raise NotImplementedError("MultinoulliNLL over n_indep > 1 takes the plain sparse "
+                                      "target only: the other options have no defined meaning "
+                                      "for several independent softmaxes")
         if weakness:
             raise NotImplementedError("weak training (weakness != 0) is outside the HIP "
                                       "hot path")
@@ -151,6 +163,14 @@ class MultinoulliNLL(Node):
         self.n_indep = pred.n_indep
         self.target_is_sparse = target_is_sparse
         k = self.n_class
+        if self.n_indep != 1:
+            want = tuple(self.n_indep if t == 'f' else s
+                         for s, t in zip(pred.shape.shape, pred.shape.tags))
+            if tuple(target.shape.tags) != tuple(pred.shape.tags) or \
+                    tuple(target.shape.shape) != want:
+                raise ValueError("MultinoulliNLL over %i independent softmaxes: the sparse target "
+                                 "must be %s (one class id per softmax) for the prediction %s, "
+                                 "got %s" % (self.n_indep, want, pred.shape, target.shape))
         if cw_param is not None:
             if cw_param.shape != (k,):
                 raise ValueError("class_weights: %i values given, the prediction has %i "
@@ -270,6 +290,10 @@ class MultinoulliNLL(Node):
                               plan.out[self.target], plan.out[self.pred], stats,
                               weights=self._weights(plan))
             return
+        if self.n_indep != 1:                # every group in one launch (csrc/nll_grouped.hip)
+            plan.ctx.softmax_nll_grouped_fwd(plan.out[self.pred.parent], plan.out[self.target],
+                                             plan.out[self.pred], self.n_indep, stats)
+            return
         plan.ctx.softmax_nll_fwd(plan.out[self.pred.parent], plan.out[self.target],
                                  plan.out[self.pred], stats, weights=self._weights(plan))
 
@@ -303,6 +327,11 @@ class MultinoulliNLL(Node):
         dst, first = plan.grad_slot(logits)
         if not first:
             raise NotImplementedError("logits consumed by several nodes")
+        if self.n_indep != 1:
+            plan.ctx.softmax_nll_grouped_bwd(plan.out[self.pred], plan.out[self.target],
+                                             self.n_indep, plan.scratch[self.pred, 'stats'], dst,
+                                             plan.scratch[self, 'loss'])
+            return
         plan.ctx.softmax_nll_bwd(plan.out[self.pred], plan.out[self.target],
                                  plan.scratch[self.pred, 'stats'], dst,
                                  plan.scratch[self, 'loss'], weights=self._weights(plan))
@@ -718,11 +747,16 @@ class _Errors(Node):
         pass
 
     def host_value(self, plan):
-        """mean(int16(target) != argmax_f(pred))  (loss.py:789-817); evaluated
+        """mean(int16(target) != argmax_f(pred))  (loss.py:789-817), the argmax inside each
+        group of ``n_class`` features for ``n_indep > 1`` (loss.py:737-748); evaluated
         with torch ops on the device tensors, outside any captured graph."""
         import torch
         probs = plan.out[self.cls.pred]
-        cls = torch.argmax(probs, dim=1, keepdim=True)
+        if self.n_indep != 1:
+            sh = probs.shape
+            cls = torch.argmax(probs.reshape(sh[0], self.n_indep, self.n_class, *sh[2:]), dim=2)
+        else:
+            cls = torch.argmax(probs, dim=1, keepdim=True)
         gt = plan.out[self.target].to(torch.int16).to(cls.dtype)
         return np.float32((gt != cls).float().mean().item())
 

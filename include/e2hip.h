@@ -473,6 +473,32 @@ int e2_softmax_nll_bwd(e2_ctx*, const e2_tensor5* probs,
                        const e2_tensor5* target, const float* stats,
                        const e2_tensor5* dlogits, float* loss_out);
 
+/* ---- MultinoulliNLL over E = n_indep independent softmaxes (Softmax(parent, n_indep = E),
+ *      loss.py:82-92; sparse targets, loss.py:275-285; one normaliser, loss.py:338-346), one
+ *      launch per direction for all groups and batch items.  logits / probs / dlogits are
+ *      (n, E*k, d, h, w): group g owns features g*k .. g*k+k-1 and has a softmax of its own;
+ *      target is (n, E, d, h, w), float class ids of group g in feature g.  With
+ *        T[n,g,v] = 1 if target[n,g,v] == c for an integer c in [0,k), else 0 (negative, >= k
+ *                   and non-integer ids are unlabelled)
+ *      the forward writes probs and ADDS to stats = {loss_sum, n_lab} (zeroed by the caller):
+ *        loss_sum = sum_{T = 1} -log(p[n, g*k + target, v] + 1e-5),   n_lab = sum T over ALL groups
+ *        loss     = loss_sum / (n_lab + 1e-5)
+ *      (the pred.size / n_indep / n_class factors of loss.py:342-346 cancel under AggregateLoss's
+ *      mean, as for n_indep = 1) and the backward writes
+ *        dlogits[n, g*k+c, v] = T * (-1/(n_lab + 1e-5) * p_t/(p_t + 1e-5)) * ([c == target] - p_c)
+ *      with the probabilities of the same group, and loss_out[0] = loss.  A group without a
+ *      labelled voxel gets zeros; nothing labelled: loss 0, gradient exactly 0.  target == NULL in
+ *      the forward: probabilities only, stats is not touched (and may be NULL).  The backward
+ *      honours e2_set_loss_grad_mode like e2_softmax_nll_bwd (sum_mode: unnormalised gradient,
+ *      count_out[0] = n_lab).  All views may be strided (channel slices of wider buffers);
+ *      dlogits may alias probs.  Errors, nothing launched: n_indep < 1, logits.c % n_indep != 0,
+ *      target.c != n_indep, batch or spatial extents that disagree. ----------------------------- */
+int e2_softmax_nll_grouped_fwd(e2_ctx*, const e2_tensor5* logits, const e2_tensor5* target,
+                               const e2_tensor5* probs, int n_indep, float* stats);
+int e2_softmax_nll_grouped_bwd(e2_ctx*, const e2_tensor5* probs, const e2_tensor5* target,
+                               int n_indep, const float* stats, const e2_tensor5* dlogits,
+                               float* loss_out);
+
 /* ---- weighted MultinoulliNLL: class / example weights and the lazy-labelling masks
  *      (loss.py:172-212 arguments, loss.py:261-347 computation; n_indep = 1, sparse targets,
  *      weakness = 0).  With t = target class id (< 0: unlabelled), w = class_w, e = example_w,
