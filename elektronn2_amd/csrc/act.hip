@@ -26,34 +26,9 @@
 // All arithmetic is f32 in forms that stay finite over the whole f32 range of v (no e^{+|v|}):
 // sigmoid through e^-|v|, soft+ as max(v, 0) + log1p(e^-|v|), elu / selu through expm1f, tanh'
 // from the tanh just computed.
-#include "common.hpp"
+#include "stream_common.hpp"
 
 namespace {
-
-// exact unsigned division of n < 2^31 by a runtime constant (as in pointwise.hip)
-struct FastDiv {
-  unsigned d, m, sh;
-};
-inline FastDiv mk_div(unsigned d) {
-  FastDiv f;
-  f.d = d;
-  if (d <= 1) { f.m = 0; f.sh = 0; return f; }
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  const unsigned long long num = 1ull << (31 + l);
-  f.m = (unsigned)((num + d - 1) / d);
-  f.sh = l - 1;
-  return f;
-}
-__device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) {
-  return f.d <= 1 ? n : (__umulhi(n, f.m) >> f.sh);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 #define E2_SELU_ALPHA 1.6732632423543772848170429916717f
 #define E2_SELU_SCALE 1.0507009873554804934193349852946f
@@ -197,10 +172,6 @@ __global__ __launch_bounds__(256) void e2act_bwd_kernel(ActP p) {
   }
 }
 
-bool same_size(const e2_tensor5* a, const e2_tensor5* b) {
-  return a->n == b->n && a->c == b->c && a->d == b->d && a->h == b->h && a->w == b->w;
-}
-
 // geometry shared by the two launches: collapse (d, h, w) over the views in `v` (nv of them)
 // want_per_cu / per_max: work-groups wanted per CU before the chunks shrink, and the largest chunk
 // in items per thread
@@ -235,13 +206,7 @@ int act_geometry(e2_ctx* ctx, const e2_tensor5* const* v, int nv, ActP& p, dim3&
   const int kb = nv == 3 ? 1 : 0, ko = nv - 1;
   p.bn = (long)v[kb]->sn; p.bc = (long)v[kb]->sc; p.br0 = s0[kb]; p.br1 = s1[kb];
   p.on = (long)v[ko]->sn; p.oc = (long)v[ko]->sc; p.or0 = s0[ko]; p.or1 = s1[ko];
-  // work-groups of up to per_max items per thread, fewer while the grid would not fill the chip
-  const unsigned long long planes = (unsigned long long)t->n * t->c;
-  const unsigned long long want =
-      (unsigned long long)want_per_cu * (unsigned long long)(ctx->num_cu > 0 ? ctx->num_cu : 256);
-  unsigned per = per_max;
-  while (per > 1 && planes * ((items + 256ull * per - 1) / (256ull * per)) < want) per >>= 1;
-  p.chunk = 256u * per;
+  p.chunk = stream_chunk(ctx, (unsigned long long)t->n * t->c, items, per_max, want_per_cu);
   grid = dim3((unsigned)((items + p.chunk - 1) / p.chunk), (unsigned)t->c, (unsigned)t->n);
   return 0;
 }

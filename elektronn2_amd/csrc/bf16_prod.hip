@@ -7,7 +7,7 @@
 // conv output (neural.py:705-712), and their backward (T.grad, model.py:182) -- write those
 // images themselves, next to (or instead of) the f32 tensor.
 //
-// Thread layout: the f32 kernels of pointwise.hip give a thread four x of ONE channel; a
+// Thread layout: the f32 kernels of maxpool.hip give a thread four x of ONE channel; a
 // channels-last pixel piece holds 8 channels of one position, so here a thread owns 8 channels x
 // TWO input x (one or two pooled outputs) of one row: 8-byte row accesses per channel, one
 // 16-byte store per pixel piece.
@@ -45,7 +45,7 @@ __device__ __forceinline__ float wave_sum_f(float v) {
 }
 
 // backward of out = act(maxpool(y) + b): dy = dL/dy (every element equal to its window maximum
-// receives the gradient; relu'(0) = 0.5), dbias += sum -- pointwise.hip's pool_bwd_fixed_kernel /
+// receives the gradient; relu'(0) = 0.5), dbias += sum -- maxpool.hip's pool_bwd_fixed_kernel /
 // act_bwd_out_kernel with the bf16 images as outputs.  NX = 2 / PX pooled outputs per thread.
 template <int PZ, int PY, int PX>
 __global__ __launch_bounds__(256) void bwd_bf16_kernel(BwP p) {

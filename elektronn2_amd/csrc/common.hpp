@@ -68,7 +68,7 @@ void e2_set_error(const char* fmt, ...);
     }                                                                        \
   } while (0)
 
-// e2_nll_weights as the loss kernels take it (pointwise.hip, head.hip, tail.hip): null = default
+// e2_nll_weights as the loss kernels take it (softmax_nll.hip, head.hip, tail.hip): null = default
 struct NllW {
   const float* cw;                  // class weights [ncls]
   const float* lab;                 // mask_class_labeled [n][ncls]
@@ -196,6 +196,6 @@ int e2i_pw_wgrad_ks(e2_ctx*, const WgradArgs& a, int MT, int NT, int S);
 int e2i_wgrad_ks(e2_ctx*, const WgradArgs& a, int MT, int NT, int S);     // the same for kernels with taps
 size_t e2i_wgrad_direct_buf_floats(const WgradArgs& a, int NT, int BP, int WK);
 
-// view helpers (pointwise.hip)
+// fill helpers (view_ops.hip, arena_ops.hip)
 int e2i_fill_view(e2_ctx*, const e2_tensor5* v, float value);
 int e2i_fill_flat(e2_ctx*, float* ptr, size_t n, float value);   // kernel fill (graph safe)

@@ -36,12 +36,6 @@ struct First {
   int tilesX, tilesY;            // tiles of 32 x 8 pooled outputs
 };
 
-__device__ __forceinline__ float ff_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // conv value at window offset (a, b):  sum_t w[T-1-t] * win[a+ty][b+tx]   (F1: flipped)
 template <int KH, int KW, int PY, int PX>
 __device__ __forceinline__ float first_conv(const float (&win)[PY + KH - 1][PX + KW - 1],

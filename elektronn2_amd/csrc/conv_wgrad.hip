@@ -26,7 +26,7 @@
 // Inner loop: "quads" of 4 k-steps.  All LDS reads of quad q+1 are issued (asm,
 // invisible to hipcc's waitcnt pass) before the MFMAs of quad q; one
 // s_waitcnt lgkmcnt(0) after the MFMAs.  Two register sets ping-pong.
-#include "common.hpp"
+#include "stream_common.hpp"
 #include <stdlib.h>
 #include <algorithm>
 #include <utility>
@@ -57,20 +57,6 @@ __device__ __forceinline__ unsigned w_lds_addr(const void* p) {
   return (unsigned)(uintptr_t)(lds_vp)p;
 }
 
-struct FastDivW { unsigned d, m, sh; };
-static inline FastDivW mk_divw(unsigned d) {
-  FastDivW f; f.d = d;
-  if (d <= 1) { f.m = 0; f.sh = 0; return f; }
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  f.m = (unsigned)(((1ull << (31 + l)) + d - 1) / d);
-  f.sh = l - 1;
-  return f;
-}
-__device__ __forceinline__ unsigned fdivw(unsigned n, const FastDivW& f) {
-  return f.d <= 1 ? n : (__umulhi(n, f.m) >> f.sh);
-}
-
 struct WgradP {
   const float* x;
   const float* dy;
@@ -90,7 +76,7 @@ struct WgradP {
   int Din, N;
   int dbg;
   int bf16;               // operands rounded to bf16 into the matrix core (padded-gradient entry only)
-  FastDivW divWo;
+  FastDiv divWo;
 };
 
 __device__ __forceinline__ f32x4 w_lds_ld128f(unsigned addr, int off_dummy = 0) {
@@ -221,8 +207,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradP p) {
     const int n = zz / p.Do;
     const int q0 = pt * BP;
     const int qlast = min(q0 + BP, p.Q) - 1;
-    const int r0 = (int)fdivw(q0, p.divWo), c0 = q0 - r0 * p.Wo;
-    const int rl = (int)fdivw(qlast, p.divWo), cl = qlast - rl * p.Wo;
+    const int r0 = (int)fdiv(q0, p.divWo), c0 = q0 - r0 * p.Wo;
+    const int rl = (int)fdiv(qlast, p.divWo), cl = qlast - rl * p.Wo;
     const long span_lo = (long)r0 * p.xsY + c0;
     const int L = (rl - r0) * xsY + (cl - c0) + (p.kh - 1) * xsY + p.kw;
     // dy rows: lane <-> position (64 positions per DMA instruction)
@@ -233,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradP p) {
       const int q = q0 + pl;
       const bool valid = q <= qlast;
       const int qc = valid ? q : qlast;
-      const int r = (int)fdivw(qc, p.divWo), c = qc - r * p.Wo;
+      const int r = (int)fdiv(qc, p.divWo), c = qc - r * p.Wo;
       // span-offset table, [qd][BP/4] so a lane reads 4 consecutive k-steps at once
       if (wave == 0) tbl[pl] = (r - r0) * xsY + (c - c0);
       const float* src = dyb + (long)r * p.dsY + c;
@@ -622,7 +608,7 @@ int e2i_wgrad_conv(e2_ctx* ctx, const WgradArgs& a) {
   p.bufFloats = (int)w_buf_floats(a, c.MT, BNn, c.BP);
   p.Din = a.Do + a.kd - 1;
   p.N = a.N;
-  p.divWo = mk_divw((unsigned)a.Wo);
+  p.divWo = mk_div((unsigned)a.Wo);
   p.dbg = e2_dbg_env_int("E2_WGRAD_DBG");
   p.bf16 = (ctx->mfma_bf16 && a.dy_padded) ? 1 : 0;
   size_t lds = 2 * (size_t)p.bufFloats * 4;

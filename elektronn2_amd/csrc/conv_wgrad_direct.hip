@@ -21,7 +21,7 @@
 // Positions past the end of a plane's span (the last one or two quads of a plane) are
 // masked out of A with v_cndmask after the load; the loads themselves may run up to
 // 31 floats past the span, hence the 128 B of slack the entry point asks for.
-#include "common.hpp"
+#include "stream_common.hpp"
 #include <stdlib.h>
 #include <algorithm>
 #include <vector>
@@ -60,20 +60,6 @@ __device__ __forceinline__ unsigned d_lds_addr(const void* p) {
   return (unsigned)(uintptr_t)(lds_vp)p;
 }
 
-struct FastDivD { unsigned d, m, sh; };
-static inline FastDivD mk_divd(unsigned d) {
-  FastDivD f; f.d = d;
-  if (d <= 1) { f.m = 0; f.sh = 0; return f; }
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  f.m = (unsigned)(((1ull << (31 + l)) + d - 1) / d);
-  f.sh = l - 1;
-  return f;
-}
-__device__ __forceinline__ unsigned fdivd(unsigned n, const FastDivD& f) {
-  return f.d <= 1 ? n : (__umulhi(n, f.m) >> f.sh);
-}
-
 struct WdP {
   const float* x;
   const float* dy;        // interior origin of the zero-padded gradient buffer
@@ -92,7 +78,7 @@ struct WdP {
   int Din, N;
   int dbg;
   int xcd;                // 1: work-groups that share gradient rows run on ONE XCD (see the kernel)
-  FastDivD divDsY;
+  FastDiv divDsY;
   unsigned long long* stamps;   // debug (E2_WGRAD_STAMPS): s_memtime stamps per work-group
 };
 
@@ -299,14 +285,14 @@ __global__ __launch_bounds__(512, 1) void wgrad_direct_kernel(WdP p) {
       const int n = zz / p.Do;
       const int s0 = pt * BP;
       const int sLast = min(s0 + BP, p.S) - 1;
-      const int r0 = (int)fdivd(s0, p.divDsY), c0 = min(s0 - r0 * dsY, p.Wo - 1);
-      const int rl = (int)fdivd(sLast, p.divDsY), cl = min(sLast - rl * dsY, p.Wo - 1);
+      const int r0 = (int)fdiv(s0, p.divDsY), c0 = min(s0 - r0 * dsY, p.Wo - 1);
+      const int rl = (int)fdiv(sLast, p.divDsY), cl = min(sLast - rl * dsY, p.Wo - 1);
       const int span_lo = r0 * xsY + c0;
       const int L = rl * xsY + cl - span_lo + (p.kh - 1) * xsY + p.kw;
       // span position -> offset inside the staged input span
       for (int i = pw * 64 + lane; i < BP; i += 256) {
         const int s = min(s0 + i, sLast);
-        const int r = (int)fdivd(s, p.divDsY);
+        const int r = (int)fdiv(s, p.divDsY);
         const int c = min(s - r * dsY, p.Wo - 1);
         tbl[i] = r * xsY + c - span_lo;
       }
@@ -677,7 +663,7 @@ int e2i_wgrad_direct(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int BP, in
   p.bufFloats = (int)e2i_wgrad_direct_buf_floats(a, NT, BP, WK);
   p.Din = a.Do + a.kd - 1;
   p.N = a.N;
-  p.divDsY = mk_divd((unsigned)a.dsY);
+  p.divDsY = mk_div((unsigned)a.dsY);
   p.dbg = e2_dbg_env_int("E2_WGRAD_DBG");
   p.xcd = xcd ? 1 : 0;
   const size_t lds = 2 * (size_t)p.bufFloats * 4;

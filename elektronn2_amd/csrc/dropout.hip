@@ -9,28 +9,9 @@
 // dense in both views (a contiguous tensor becomes one long row), which changes no j.
 // A pure stream: no LDS, no atomics, no cross-work-group traffic; the counter is advanced by a
 // launch of its own (dropout_tick_kernel) in front of the step's dropout launches.
-#include "common.hpp"
+#include "stream_common.hpp"
 
 namespace {
-
-// exact unsigned division of n < 2^31 by a runtime constant (as in pointwise.hip)
-struct FastDiv {
-  unsigned d, m, sh;
-};
-inline FastDiv mk_div(unsigned d) {
-  FastDiv f;
-  f.d = d;
-  if (d <= 1) { f.m = 0; f.sh = 0; return f; }
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  const unsigned long long num = 1ull << (31 + l);
-  f.m = (unsigned)((num + d - 1) / d);
-  f.sh = l - 1;
-  return f;
-}
-__device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) {
-  return f.d <= 1 ? n : (__umulhi(n, f.m) >> f.sh);
-}
 
 struct DropP {
   const float* src;
@@ -153,8 +134,7 @@ int dropout_launch(e2_ctx* ctx, const e2_tensor5* a, const e2_tensor5* b, int fe
   E2_REQUIRE(((uintptr_t)state & 15) == 0, "%s: state must be 16-byte aligned", who);
   E2_REQUIRE(a->n > 0 && a->c > 0 && a->d > 0 && a->h > 0 && a->w > 0,
              "%s: empty tensor (%d,%d,%d,%d,%d)", who, a->n, a->c, a->d, a->h, a->w);
-  E2_REQUIRE(a->n == b->n && a->c == b->c && a->d == b->d && a->h == b->h && a->w == b->w,
-             "%s: size mismatch", who);
+  E2_REQUIRE(same_size(a, b), "%s: size mismatch", who);
   const unsigned dim[5] = {(unsigned)a->n, (unsigned)a->c, (unsigned)a->d, (unsigned)a->h,
                            (unsigned)a->w};
   const long ss[5] = {(long)a->sn, (long)a->sc, (long)a->sd, (long)a->sh, 1};

@@ -14,7 +14,7 @@
 //             tiles in registers (one atomic per (c,ci) per work-group at the
 //             end), every thread writes its share of dx = W^T dlogits.
 // Bound: HBM (read C*S*4 B; backward also writes C*S*4 B).
-#include "common.hpp"
+#include "stream_common.hpp"
 #include "nll_w.hpp"
 #include <algorithm>
 
@@ -33,11 +33,6 @@ HView hv(const e2_tensor5* t) {
 }
 __device__ __forceinline__ long hidx(const HView& v, int n, int z, int y, int x) {
   return (long)n * v.sn + (long)z * v.sd + (long)y * v.sh + x;
-}
-__device__ __forceinline__ float h_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
 }
 
 // The kernel bodies are head_fwd_body.hpp / head_bwd_body.hpp, each compiled twice: with WT = false

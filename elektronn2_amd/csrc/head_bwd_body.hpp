@@ -120,7 +120,7 @@
   if (tid < 64) {           // wave 0 (threads >= HT hold zeros)
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-      const float sb = h_wave_sum(ab[c]);
+      const float sb = wave_sum(ab[c]);
       if (tid == 0) mine[NC * C + c] = sb;
     }
   }

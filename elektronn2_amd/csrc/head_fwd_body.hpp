@@ -63,8 +63,8 @@
     }
   }
   if (has_target) {                       // wave 0 only
-    const float a = h_wave_sum(lsum);
-    float b = h_wave_sum(nlab);
+    const float a = wave_sum(lsum);
+    float b = wave_sum(nlab);
     if constexpr (WT) {
       if (p == 0 && blockIdx.x == 0 && blockIdx.z == 0) b += head_w_count_dn(wt, x.n * NC, S);
     }

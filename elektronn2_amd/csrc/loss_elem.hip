@@ -27,34 +27,9 @@
 // and on misaligned views; axes that are dense in all views are collapsed on the host (here also
 // the feature and batch axes: there is no bias, a work-group need not stay inside one (n, c)).
 // Nothing outside a view is read or written.  Kind and options are template parameters.
-#include "common.hpp"
+#include "stream_common.hpp"
 
 namespace {
-
-// exact unsigned division of n < 2^31 by a runtime constant (as in act.hip)
-struct FastDiv {
-  unsigned d, m, sh;
-};
-inline FastDiv mk_div(unsigned d) {
-  FastDiv f;
-  f.d = d;
-  if (d <= 1) { f.m = 0; f.sh = 0; return f; }
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  const unsigned long long num = 1ull << (31 + l);
-  f.m = (unsigned)((num + d - 1) / d);
-  f.sh = l - 1;
-  return f;
-}
-__device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) {
-  return f.d <= 1 ? n : (__umulhi(n, f.m) >> f.sh);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 #define E2_LOSS_EPS 1e-5f
 #define E2_LOSS_MASK_TOL (1e-8f + 666e-5f)
@@ -325,10 +300,6 @@ __global__ __launch_bounds__(256) void e2loss_mix_kernel(MixP p) {
     }
   }
   if (tid == 0) p.loss_out[0] = (float)(total / (double)p.k);
-}
-
-bool same_size(const e2_tensor5* a, const e2_tensor5* b) {
-  return a->n == b->n && a->c == b->c && a->d == b->d && a->h == b->h && a->w == b->w;
 }
 
 // work-groups of a launch over this many elements: 2048 elements (two quads per thread) each, at

@@ -17,28 +17,9 @@
 // are collapsed on the host: rows of w with (py, 0) padding become one row of h * w with
 // py * w padding elements at either end.  Nothing outside the dst view is written, nothing
 // outside the src view is read.  Pure stream: no LDS, no workspace.
-#include "common.hpp"
+#include "stream_common.hpp"
 
 namespace {
-
-// exact unsigned division of n < 2^31 by a runtime constant (as in act.hip)
-struct FastDiv {
-  unsigned d, m, sh;
-};
-inline FastDiv mk_div(unsigned d) {
-  FastDiv f;
-  f.d = d;
-  if (d <= 1) { f.m = 0; f.sh = 0; return f; }
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  const unsigned long long num = 1ull << (31 + l);
-  f.m = (unsigned)((num + d - 1) / d);
-  f.sh = l - 1;
-  return f;
-}
-__device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) {
-  return f.d <= 1 ? n : (__umulhi(n, f.m) >> f.sh);
-}
 
 // the (d, h, w) block of one (n, c) of dst after the host's collapse
 struct PadP {
@@ -159,12 +140,7 @@ extern "C" int e2_pad5(e2_ctx* ctx, const e2_tensor5* src, const e2_tensor5* dst
   p.quads = (unsigned)quads; p.items = (unsigned)items;
   p.dq = mk_div(p.quads); p.dh = mk_div(p.H);
   p.value = value;
-  // work-groups of up to 8 items per thread, fewer while the grid would not fill the chip
-  const unsigned long long planes = (unsigned long long)dst->n * dst->c;
-  const unsigned long long want = 8ull * (unsigned long long)(ctx->num_cu > 0 ? ctx->num_cu : 256);
-  unsigned per = 8;
-  while (per > 1 && planes * ((items + 256ull * per - 1) / (256ull * per)) < want) per >>= 1;
-  p.chunk = 256u * per;
+  p.chunk = stream_chunk(ctx, (unsigned long long)dst->n * dst->c, items, 8, 8);
   const dim3 grid((unsigned)((items + p.chunk - 1) / p.chunk), (unsigned)dst->c, (unsigned)dst->n);
   if (frame_only)
     hipLaunchKernelGGL((e2pad_kernel<true>), grid, dim3(256), 0, ctx->stream, p);

@@ -22,28 +22,9 @@
 // is added to the accumulators of the quad elements whose range holds it.  Nothing outside the
 // destination view is written, nothing outside the source view is read.  Pure stream: no LDS, no
 // workspace; window and stride are runtime values, the mode is a template parameter.
-#include "common.hpp"
+#include "stream_common.hpp"
 
 namespace {
-
-// exact unsigned division of n < 2^31 by a runtime constant (as in act.hip)
-struct FastDiv {
-  unsigned d, m, sh;
-};
-inline FastDiv mk_div(unsigned d) {
-  FastDiv f;
-  f.d = d;
-  if (d <= 1) { f.m = 0; f.sh = 0; return f; }
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  const unsigned long long num = 1ull << (31 + l);
-  f.m = (unsigned)((num + d - 1) / d);
-  f.sh = l - 1;
-  return f;
-}
-__device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) {
-  return f.d <= 1 ? n : (__umulhi(n, f.m) >> f.sh);
-}
 
 // s: the tensor that is read (x / dout), o: the tensor that is written (out / dx)
 struct PoolP {
@@ -295,15 +276,6 @@ void e2pool_lin_bwd_kernel(PoolP p) {
   }
 }
 
-int view_ok(const e2_tensor5* t, const char* who, const char* what) {
-  E2_REQUIRE(t && t->ptr, "%s: null %s", who, what);
-  E2_REQUIRE(t->n > 0 && t->c > 0 && t->d > 0 && t->h > 0 && t->w > 0,
-             "%s: empty %s (%d,%d,%d,%d,%d)", who, what, t->n, t->c, t->d, t->h, t->w);
-  E2_REQUIRE((unsigned long long)t->d * t->h * t->w < (1ull << 31),
-             "%s: a channel of %s holds 2^31 elements or more", who, what);
-  return 0;
-}
-
 // big: the unpooled tensor (x / dx), small: the pooled one (out / dout)
 int geometry_ok(const char* who, const e2_tensor5* big, const e2_tensor5* small, int pz, int py,
                 int px, int sz, int sy, int sx, int mode) {
@@ -319,8 +291,9 @@ int geometry_ok(const char* who, const e2_tensor5* big, const e2_tensor5* small,
              "%s: (%d,%d,%d,%d,%d) pooled by %d,%d,%d stride %d,%d,%d is not (%d,%d,%d,%d,%d)", who,
              big->n, big->c, big->d, big->h, big->w, pz, py, px, sz, sy, sx, small->n, small->c,
              small->d, small->h, small->w);
-  E2_REQUIRE(big->c <= 65535 && big->n <= 65535, "%s: more than 65535 features / batch entries",
-             who);
+  E2_REQUIRE((unsigned long long)big->d * big->h * big->w < (1ull << 31),
+             "%s: a channel of (%d,%d,%d,%d,%d) holds 2^31 elements or more", who, big->n, big->c,
+             big->d, big->h, big->w);
   // (32-bit index math: 5 * extent stays below 2^31)
   E2_REQUIRE(big->d < (1 << 28) && big->h < (1 << 28) && big->w < (1 << 28),
              "%s: feature map too large", who);
@@ -347,12 +320,7 @@ PoolP mk_params(e2_ctx* ctx, const e2_tensor5* src, const e2_tensor5* dst, int p
   p.dq = mk_div(p.quads); p.dh = mk_div(p.H);
   p.dtz = mk_div(p.tz); p.dty = mk_div(p.ty); p.dtx = mk_div(p.tx);
   p.scale = mode == E2_POOL_AVG ? 1.0f / (float)((long)pz * py * px) : 1.0f;
-  // work-groups of up to 8 items per thread, fewer while the grid would not fill the chip
-  const unsigned long long planes = (unsigned long long)dst->n * dst->c;
-  const unsigned long long want = 8ull * (unsigned long long)(ctx->num_cu > 0 ? ctx->num_cu : 256);
-  unsigned per = 8;
-  while (per > 1 && planes * ((items + 256ull * per - 1) / (256ull * per)) < want) per >>= 1;
-  p.chunk = 256u * per;
+  p.chunk = stream_chunk(ctx, (unsigned long long)dst->n * dst->c, items, 8, 8);
   *grid = dim3((unsigned)((items + p.chunk - 1) / p.chunk), (unsigned)dst->c, (unsigned)dst->n);
   return p;
 }
@@ -363,8 +331,8 @@ extern "C" int e2_pool3d_lin_fwd(e2_ctx* ctx, const e2_tensor5* x, int pz, int p
                                  int sy, int sx, int mode, const e2_tensor5* out) {
   const char* who = "e2_pool3d_lin_fwd";
   E2_REQUIRE(ctx, "%s: null ctx", who);
-  if (int rc = view_ok(x, who, "x")) return rc;
-  if (int rc = view_ok(out, who, "out")) return rc;
+  if (int rc = check_view(x, "e2_pool3d_lin_fwd x")) return rc;
+  if (int rc = check_view(out, "e2_pool3d_lin_fwd out")) return rc;
   if (int rc = geometry_ok(who, x, out, pz, py, px, sz, sy, sx, mode)) return rc;
   E2_REQUIRE(((unsigned long long)out->d * out->h) * ((unsigned long long)(out->w + 3) / 4 + 1) <
                  (1ull << 31), "%s: feature map too large", who);
@@ -394,8 +362,8 @@ extern "C" int e2_pool3d_lin_bwd(e2_ctx* ctx, const e2_tensor5* dout, int pz, in
                                  int accumulate) {
   const char* who = "e2_pool3d_lin_bwd";
   E2_REQUIRE(ctx, "%s: null ctx", who);
-  if (int rc = view_ok(dout, who, "dout")) return rc;
-  if (int rc = view_ok(dx, who, "dx")) return rc;
+  if (int rc = check_view(dout, "e2_pool3d_lin_bwd dout")) return rc;
+  if (int rc = check_view(dx, "e2_pool3d_lin_bwd dx")) return rc;
   if (int rc = geometry_ok(who, dx, dout, pz, py, px, sz, sy, sx, mode)) return rc;
   E2_REQUIRE(((unsigned long long)dx->d * dx->h) * ((unsigned long long)(dx->w + 3) / 4 + 1) <
                  (1ull << 31), "%s: feature map too large", who);

@@ -1,5 +1,5 @@
-// body of softmax_nll_bwd_kernel / softmax_nll_bwd_w_kernel (pointwise.hip) and of
-// softmax_nll_grouped_bwd_kernel (nll_grouped.hip): in scope are the flag WT, the kernel's
+// body of softmax_nll_bwd_kernel / softmax_nll_bwd_w_kernel and of
+// softmax_nll_grouped_bwd_kernel (softmax_nll.hip): in scope are the flag WT, the kernel's
 // arguments and `NllW wt`.
   const long S = (long)pr.d * pr.h * pr.w;
   const long s = blockIdx.x * 256L + threadIdx.x;

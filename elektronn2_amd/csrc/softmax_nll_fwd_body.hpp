@@ -1,5 +1,5 @@
-// body of softmax_nll_fwd_kernel / softmax_nll_fwd_w_kernel (pointwise.hip) and of
-// softmax_nll_grouped_fwd_kernel (nll_grouped.hip): in scope are the flags WT and HAS_T (false:
+// body of softmax_nll_fwd_kernel / softmax_nll_fwd_w_kernel and of
+// softmax_nll_grouped_fwd_kernel (softmax_nll.hip): in scope are the flags WT and HAS_T (false:
 // no target, probabilities only), the kernel's arguments and `NllW wt`.
   __shared__ float red[4];
   const long S = (long)lg.d * lg.h * lg.w;

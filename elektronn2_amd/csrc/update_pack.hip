@@ -25,25 +25,16 @@
 // adam_kernel's float4 sweep reaches 4.6 TB/s (42 vs 17.6 us without the image writes), and the
 // image writes alone take what pack_multi_kernel takes (36 us with zeros as source).  Kept as an
 // entry point, plan option adam_pack OFF.
-#include "common.hpp"
+#include "stream_common.hpp"
 #include <algorithm>
 
 #define E2_EPS_ADAM 1e-5f
 
 namespace {
 
-struct UDiv { unsigned d, m, sh; };       // n / d == umulhi(n, m) >> sh  (n < 2^31)
-inline UDiv mk_udiv(unsigned d) {
-  UDiv f; f.d = d;
-  if (d <= 1) { f.m = 0; f.sh = 0; return f; }
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  f.m = (unsigned)(((1ull << (31 + l)) + d - 1) / d);
-  f.sh = l - 1;
-  return f;
-}
-__device__ __forceinline__ int udiv(int n, const UDiv& f) {
-  return f.d <= 1 ? n : (int)(__umulhi((unsigned)n, f.m) >> f.sh);
+// (signed operands below 2^31: the tile and element indices of the kernel are ints)
+__device__ __forceinline__ int udiv(int n, const FastDiv& f) {
+  return (int)fdiv((unsigned)n, f);
 }
 
 struct UpdJob {
@@ -57,7 +48,7 @@ struct UpdJob {
   int nOT, nIT;             // tiles along cout / cin (x kd planes)
   int tile0;                // first tile of this job in the launch's tile sequence
   float reg;                // weight-decay multiplier of the tensor (0: none)
-  UDiv dKT, dTHW, dIC, dOT, dOTIT;
+  FastDiv dKT, dTHW, dIC, dOT, dOTIT;
 };
 
 struct UpdRest { long off, n; float reg; int pad; };
@@ -248,8 +239,8 @@ extern "C" int e2_upd_job_fill(void* rec, long off, void* wp_f, void* wp_d, int 
   j->nOT = (std::max(ocR, cout) + 31) / 32;
   j->nIT = (std::max(icR, cin) + j->IC - 1) / j->IC;
   j->tile0 = tile0; j->reg = reg;
-  j->dKT = mk_udiv(j->IC * j->THW); j->dTHW = mk_udiv(j->THW); j->dIC = mk_udiv(j->IC);
-  j->dOT = mk_udiv(j->nOT); j->dOTIT = mk_udiv(j->nOT * j->nIT);
+  j->dKT = mk_div(j->IC * j->THW); j->dTHW = mk_div(j->THW); j->dIC = mk_div(j->IC);
+  j->dOT = mk_div(j->nOT); j->dOTIT = mk_div(j->nOT * j->nIT);
   const long nt = (long)j->nOT * j->nIT * kd;
   E2_REQUIRE(nt + tile0 < (1L << 30) && (long)32 * j->IC * j->THW < (1L << 30), "upd_job_fill: tensor too large");
   *ntiles = (int)nt;

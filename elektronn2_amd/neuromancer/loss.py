@@ -16,7 +16,7 @@ The weight Inputs are ordinary inputs of the loss node: extra positional argumen
 ``trainingstep(data, target, *extras)`` in the order of ``loss_node.input_nodes``, slices of the
 plan's input arena (and of an input-ring slot).  Whichever kernel the plan chose for the loss --
 the fused tail (csrc/tail.hip), the fused head (csrc/head.hip) or the generic pair
-(csrc/pointwise.hip) -- takes the weights (the ``_w`` entry points of include/e2hip.h).
+(csrc/softmax_nll.hip) -- takes the weights (the ``_w`` entry points of include/e2hip.h).
 The weighted tail launch is f32 only: in bf16 mode (``set_mfma_dtype('bf16')``) a neuro3d-style net
 with a weighted loss needs the plan option ``bf16_tail`` off (the separate kernels then run; the
 choice of the path never depends on the weights, so the launch reports an error otherwise).
@@ -28,7 +28,7 @@ loss.py:82-92) trains under ``MultinoulliNLL(..., target_is_sparse=True)`` with 
 (loss.py:275-285, 338-346):
     loss = sum over the labelled (item, group, position) of -log(p_target + 1e-5)
            / (n_labelled + 1e-5),      ONE count over all groups,
-one forward and one backward launch for all groups (csrc/nll_grouped.hip).  The fused head and
+one forward and one backward launch for all groups (csrc/softmax_nll.hip).  The fused head and
 tail step aside for such a softmax; class / example weights and the class masks with
 ``n_indep > 1`` raise NotImplementedError (the reference broadcasts a length-n_class vector
 against E * n_class features).  ``Errors`` of such a net compares the argmax inside each group
@@ -290,7 +290,7 @@ class MultinoulliNLL(Node):
                               plan.out[self.target], plan.out[self.pred], stats,
                               weights=self._weights(plan))
             return
-        if self.n_indep != 1:                # every group in one launch (csrc/nll_grouped.hip)
+        if self.n_indep != 1:                # every group in one launch (csrc/softmax_nll.hip)
             plan.ctx.softmax_nll_grouped_fwd(plan.out[self.pred.parent], plan.out[self.target],
                                              plan.out[self.pred], self.n_indep, stats)
             return

@@ -1526,7 +1526,7 @@ UpConvMerge = AutoMerge
 class Pool(Node):
     """Pooling node (neural.py:1409-1559).
 
-    ``mode``: 'max' (csrc/pointwise.hip, ``stride`` None or == ``pool_shape``), or one of the
+    ``mode``: 'max' (csrc/maxpool.hip, ``stride`` None or == ``pool_shape``), or one of the
     linear modes 'average' (stored as 'average_inc_pad', neural.py:1454-1455), 'average_inc_pad',
     'average_exc_pad' (no padding here: the same as inc_pad) and 'sum' (csrc/pool.hip).  The linear
     modes take any ``stride`` >= 1 per axis: overlapping windows below the pool extent, gaps above

@@ -277,7 +277,7 @@ def test_unet3d_lite_native_size():
     """BASELINE configs[2]: examples/unet3d_lite.py at its own (1,1,22,140,140) ->
     (1,2,10,52,52), 398 GF per step; then the captured hipGraphs are replayed: loss and
     gradients must stay put (a hipMemsetAsync node re-ordered against the split-K kernel
-    behind it once broke exactly this, see csrc/pointwise.hip e2i_fill_flat)."""
+    behind it once broke exactly this, see csrc/arena_ops.hip e2i_fill_flat)."""
     from elektronn2_amd import nets, neuromancer as nm
     nm.model_manager.reset()
     np.random.seed(5)

@@ -1,5 +1,5 @@
 """MultinoulliNLL over several independent softmaxes on the GPU: the one-launch kernels
-e2_softmax_nll_grouped_fwd / _bwd (csrc/nll_grouped.hip) through the C ABI, and nets whose last
+e2_softmax_nll_grouped_fwd / _bwd (csrc/softmax_nll.hip) through the C ABI, and nets whose last
 layer is ``Softmax(n_indep=E)`` under ``MultinoulliNLL(target_is_sparse=True)``.
 
 The reference of every comparison is the float64 loop restatement of the contract in

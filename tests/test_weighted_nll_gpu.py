@@ -1,6 +1,6 @@
 """The weighted MultinoulliNLL -- class weights, example weights, mask_class_labeled,
 mask_class_not_present (reference loss.py:172-212, 261-347) -- on the device: the three kernel
-pairs through the C ABI (generic pair of csrc/pointwise.hip, fused head of csrc/head.hip, fused
+pairs through the C ABI (generic pair of csrc/softmax_nll.hip, fused head of csrc/head.hip, fused
 tail of csrc/tail.hip), then whole training steps on the three paths.
 
 The reference of every comparison is ``ref_loss`` below: a float64 torch-CPU restatement of
