@@ -252,7 +252,8 @@ def wgrad_candidates(cout, cin, k, out_sp, n_cu=256):
                             # group count: csrc/conv_wgrad_direct.hip)
                             cands.append("%d,%d,%d,%d,%d" % (mt, nt, wk + 100, bp, q))
     return sorted(set(cands) | set(pointwise_wgrad_candidates(cout, cin, k, out_sp, n_cu))
-                  | set(position_split_wgrad_candidates(cout, cin, k, out_sp, n_cu)))
+                  | set(position_split_wgrad_candidates(cout, cin, k, out_sp, n_cu))
+                  | set(even_split_wgrad_candidates(cout, cin, k, out_sp, n_cu)))
 
 
 WGRAD_KS_TILES = [(13, 2), (10, 2), (8, 2), (8, 4), (7, 2), (7, 4), (6, 4), (5, 4), (4, 4), (3, 4), (2, 4)]
@@ -281,6 +282,43 @@ def position_split_wgrad_candidates(cout, cin, k, out_sp, n_cu=256):
         for fill in (0.5, 1, 2):
             s = max(1, min(-(-units // 4), int(n_cu * fill) // tiles))
             out.append("%d,%d,9,0,%d" % (mt, nt, s))
+    return sorted(set(out))
+
+
+def even_split_wgrad_candidates(cout, cin, k, out_sp, n_cu=256):
+    """"MT,NT,9,B,G" / "MT,NT,8,B,G", B >= 1: the tiles of the two position-split forms with EVEN
+    position ranges (csrc/wgrad_even.hpp) -- G work-groups share the tiles x units pairs, so the
+    grid fills the chip whatever the tile count: G = CUs x r for r = 1, 2 where a work-group's LDS
+    (its four partial tiles, 4 x 16 MT x (16 NT + 4) floats of 160 KB per CU) allows two per CU,
+    for the tiles that waste the fewest MFMAs (the registers allow two work-groups per CU at
+    most as well, but for the 2 x 4 and 3 x 4 tiles).  B = 1 orders the pairs tile by tile; B > 1
+    band by band of positions, with as many bands as the position-split form would take splits
+    to reach G work-groups (the tiles of one band then share the gradient rows in L2)"""
+    T = k[0] * k[1] * k[2]
+    if T == 1:
+        if cout < 32 or cin < 32 or out_sp[0] * out_sp[1] * out_sp[2] < 32:
+            return []
+        tiles, form = PW_WGRAD_KS_TILES, 8
+        units = out_sp[0] * out_sp[1] * out_sp[2] // 32     # (of ONE sample; the library refuses B > units)
+    else:
+        if not position_split_wgrad_candidates(cout, cin, k, out_sp, n_cu):
+            return []
+        tiles, form = WGRAD_KS_TILES, 9
+        pitch = out_sp[2] + k[2] - 1
+        units = out_sp[0] * (-(-((out_sp[1] - 1) * pitch + out_sp[2]) // 32))
+    scored = []
+    for mt, nt in tiles:
+        nm, nn = -(-cout // (16 * mt)), -(-(cin * T) // (16 * nt))
+        eff = (cout * cin * T) / float(nm * 16 * mt * nn * 16 * nt)
+        scored.append((-eff, -mt * nt, mt, nt, nm * nn))
+    scored.sort()
+    out = []
+    for _, _, mt, nt, ntiles in scored[:3]:
+        lds = 4 * 16 * mt * (16 * nt + 4) * 4
+        for r in range(1, min(2, (160 * 1024) // lds) + 1):
+            g = n_cu * r
+            for b in sorted({1, max(1, min(-(-units // 4), g // ntiles))}):
+                out.append("%d,%d,%d,%d,%d" % (mt, nt, form, b, g))
     return sorted(set(out))
 
 

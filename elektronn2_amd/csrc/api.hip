@@ -83,9 +83,9 @@ extern "C" int e2_set_loss_grad_mode(e2_ctx* ctx, int sum_mode, float* count_out
 
 /* The caller vouches that the input tensor x of the conv launches that follow is followed by at
  * least `bytes` readable bytes holding FINITE values (its own allocation's zeroed slack, or more
- * of the buffer a view was cut from): the weight gradient "MT,NT,9,0,S" lets the last 32-position
- * unit of a plane run past the plane's end -- the gradient's zero border times whatever x holds
- * there -- and is offered only with >= 128.  0 (the default) withdraws the promise. */
+ * of the buffer a view was cut from): the weight gradient "MT,NT,9,0,S" (and its even form
+ * "MT,NT,9,B,G") lets the last 32-position unit of a plane run past the plane's end -- the
+ * gradient's zero border times whatever x holds there -- and is offered only with >= 128.  0 (the default) withdraws the promise. */
 extern "C" int e2_set_input_slack(e2_ctx* ctx, int bytes) {
   E2_REQUIRE(ctx && bytes >= 0, "e2_set_input_slack: bad argument");
   ctx->input_slack = bytes;

@@ -192,8 +192,9 @@ int e2i_wgrad_direct(e2_ctx*, const WgradArgs& a, int MT, int NT, int BP, int PS
 int e2i_wgrad_direct_lpad(const WgradArgs& a, int BP);
 // conv_pw_wgrad.hip: 1x1x1 / UpConv weight gradient as a GEMM with K-contiguous operands
 int e2i_pw_wgrad(e2_ctx*, const WgradArgs& a, int MT, int NT, int S);
-int e2i_pw_wgrad_ks(e2_ctx*, const WgradArgs& a, int MT, int NT, int S);
-int e2i_wgrad_ks(e2_ctx*, const WgradArgs& a, int MT, int NT, int S);     // the same for kernels with taps
+// (even = B >= 1: S work-groups with even position ranges in B bands, wgrad_even.hpp)
+int e2i_pw_wgrad_ks(e2_ctx*, const WgradArgs& a, int MT, int NT, int S, int even);
+int e2i_wgrad_ks(e2_ctx*, const WgradArgs& a, int MT, int NT, int S, int even);     // the same for kernels with taps
 size_t e2i_wgrad_direct_buf_floats(const WgradArgs& a, int NT, int BP, int WK);
 
 // fill helpers (view_ops.hip, arena_ops.hip)

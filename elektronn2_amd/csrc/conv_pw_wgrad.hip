@@ -23,6 +23,7 @@
 // Tiling "MT,NT,7,0,S" through e2_set_tiling(E2_TILING_WGRAD, ...); never chosen untuned.
 // Requires dense channel planes (row stride = W, plane stride = H * W) for x and dy.
 #include "common.hpp"
+#include "wgrad_even.hpp"
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -350,6 +351,251 @@ __global__ __launch_bounds__(256) void pw_wgrad_ks_kernel(PgP p) {
 #endif
 }
 
+// ---- the same tile, EVEN position ranges ("MT,NT,8,B,G" / "MT,NT,9,B,G", B >= 1 bands) ----------
+// The grid above is tiles x S: it fills the chip only where that product happens to be close to
+// CUs x residency (57 tiles x 4 = 228 work-groups for 256 CUs).  Here G work-groups share the
+// tiles x units pairs evenly (wgrad_even.hpp); a work-group whose range crosses a tile boundary
+// runs one segment per tile -- zero, multiply, sum through LDS, flush with atomics -- so a tile
+// has any number of producers.  A kernel of its own: pw_wgrad_ks_kernel keeps its instruction
+// stream.  The segment loop has ONE exit and is never unrolled (DESIGN.md lessons 5 and 10).
+template <int MT, int NT, bool TAPS>
+__global__ __launch_bounds__(256) void pw_wgrad_ev_kernel(PgP p, WgEven ev) {
+  extern __shared__ float red[];
+  constexpr int RW = 16 * NT + 4;                    // padded row of a wave's partial tile
+  constexpr int RS = 16 * MT * RW;
+  const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, q = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // work-groups b, b + 8, b + 16 ... share an XCD: consecutive ranges -- the tiles of one band of
+  // positions -- run THERE, so a gradient row comes out of HBM once per band, not once per tile
+  int g = blockIdx.x;
+  if ((ev.G & 7) == 0) g = (g & 7) * (ev.G >> 3) + (g >> 3);
+  WgRange rg = wg_even_range(ev, g);
+  if (rg.b >= rg.e) return;                          // (more work-groups than pairs)
+  KS_STAMP(0);
+#ifdef E2_DEBUG_ENV
+  int nseg = 0;
+#endif
+#pragma unroll 1
+  do {
+    const WgSeg sg = wg_even_seg(ev, rg);
+    const int mt = sg.tile / p.nNT, nt = sg.tile - mt * p.nNT;
+    const int m0 = mt * 16 * MT, n0 = nt * 16 * NT;
+    const int u0 = sg.u0 + wave, u1 = sg.u0 + sg.n;
+    const int cnt = u0 < u1 ? (u1 - u0 + 3) >> 2 : 0;
+
+    // BYTE offsets of the lane's rows inside a sample (32 bits: checked by the host)
+    unsigned aoff[MT], boff[NT];
+#pragma unroll
+    for (int mb = 0; mb < MT; ++mb) aoff[mb] = (unsigned)min(m0 + 16 * mb + l15, p.M - 1) * (unsigned)p.asC * 4u + 16u * q;
+#pragma unroll
+    for (int nb = 0; nb < NT; ++nb) {
+      const int j = min(n0 + 16 * nb + l15, p.Ncol - 1);
+      if (TAPS) {
+        const int ci = j / p.T, ts = j - ci * p.T;
+        const int t = p.flip ? p.T - 1 - ts : ts;
+        const int tz = t / (p.kh * p.kw), r2 = t - tz * (p.kh * p.kw);
+        const int ty = r2 / p.kw, tx = r2 - ty * p.kw;
+        const unsigned row = (unsigned)ci * (unsigned)p.bsC * 4u;
+        boff[nb] = row + (unsigned)(tz * p.bsZ + ty * p.bsY + tx) * 4u + 16u * q;
+      } else {
+        boff[nb] = (unsigned)j * (unsigned)p.bsC * 4u + 16u * q;
+      }
+    }
+
+    f32x4 acc[MT][NT];
+#pragma unroll
+    for (int mb = 0; mb < MT; ++mb)
+#pragma unroll
+      for (int nb = 0; nb < NT; ++nb) acc[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // unit i of this wave in this segment (see pw_wgrad_ks_kernel: whole units, TAPS: of a plane)
+    auto where = [&](int i, const char*& ap, const char*& bp, unsigned& kb, unsigned& zb) {
+      const int u = u0 + 4 * i;
+      const int pl = u / p.stepsPerSample;
+      kb = (unsigned)(u - pl * p.stepsPerSample) * 128u;
+      if (TAPS) {
+        const int n = pl / p.planes, z = pl - n * p.planes;
+        ap = reinterpret_cast<const char*>(p.a + (long)n * p.asN + (long)z * p.asZ);
+        bp = reinterpret_cast<const char*>(p.b + (long)n * p.bsN);
+        zb = (unsigned)(z * p.bsZ) * 4u;
+      } else {
+        ap = reinterpret_cast<const char*>(p.a + (long)pl * p.asN);
+        bp = reinterpret_cast<const char*>(p.b + (long)pl * p.bsN);
+        zb = 0;
+      }
+    };
+    auto bo = [&](int nb, unsigned kb, unsigned zb) -> unsigned {
+      return TAPS ? boff[nb] + zb + kb : boff[nb] + kb;
+    };
+    auto load2 = [&](f32x4 (&d)[2], const char* base, unsigned off) {
+      const char* r = base + off;                    // (4-byte aligned only)
+      __builtin_memcpy(&d[0], r, 16);
+      __builtin_memcpy(&d[1], r + 64, 16);
+    };
+
+    if (cnt > 0) {
+      f32x4 A[MT][2], Bc[NT][2], Bn[NT][2];
+      const char *ap, *bp;
+      unsigned kb, zb;
+      where(0, ap, bp, kb, zb);
+#pragma unroll
+      for (int nb = 0; nb < NT; ++nb) load2(Bc[nb], bp, bo(nb, kb, zb));
+#pragma unroll
+      for (int mb = 0; mb < MT; ++mb) load2(A[mb], ap, aoff[mb] + kb);
+      // ONE loop body; the last trip requests its own unit again (L1 / L2 hits, nothing waits)
+#pragma unroll 1
+      for (int i = 0; i < cnt; ++i) {
+        where(min(i + 1, cnt - 1), ap, bp, kb, zb);
+#pragma unroll
+        for (int nb = 0; nb < NT; ++nb) load2(Bn[nb], bp, bo(nb, kb, zb));
+#pragma unroll
+        for (int mb = 0; mb < MT; ++mb) {
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+              for (int nb = 0; nb < NT; ++nb)
+                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[mb][h][j], Bc[nb][h][j], acc[mb][nb], 0, 0, 0);
+          load2(A[mb], ap, aoff[mb] + kb);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int nb = 0; nb < NT; ++nb) { Bc[nb][0] = Bn[nb][0]; Bc[nb][1] = Bn[nb][1]; }
+      }
+    }
+    // ---- the K % 32 last positions of every sample: one masked step of the segment that holds
+    // the tile's LAST unit -- exactly one owner per tile (see pw_wgrad_ks_kernel)
+    if (!TAPS && u1 == ev.U && p.rem > 0) {
+      constexpr int MBW = (MT + 3) / 4;
+      const int k = p.K - p.rem + 4 * q;
+#pragma unroll 1
+      for (int n = 0; n < p.N; ++n) {
+        float av[MBW][8], bv[NT][8];
+        auto mload = [&](float (&d)[8], const float* row) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const int pos = k + (e >> 2) * 16 + (e & 3);
+            const float v = row[min(pos, p.K - 1)];
+            d[e] = pos < p.K ? v : 0.f;
+          }
+        };
+#pragma unroll
+        for (int nb = 0; nb < NT; ++nb)
+          mload(bv[nb], p.b + (long)n * p.bsN + (long)min(n0 + 16 * nb + l15, p.Ncol - 1) * p.bsC);
+#pragma unroll
+        for (int i = 0; i < MBW; ++i)
+          mload(av[i], p.a + (long)n * p.asN + (long)min(m0 + 16 * min(wave + 4 * i, MT - 1) + l15, p.M - 1) * p.asC);
+#pragma unroll
+        for (int mb = 0; mb < MT; ++mb)
+          if ((mb & 3) == wave) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+#pragma unroll
+              for (int nb = 0; nb < NT; ++nb)
+                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mb >> 2][e], bv[nb][e], acc[mb][nb], 0, 0, 0);
+          }
+      }
+    }
+
+    // ---- the four partial tiles through LDS, then atomics: a tile has other producers ---------
+    float* mine = red + wave * RS;
+#pragma unroll
+    for (int mb = 0; mb < MT; ++mb)
+#pragma unroll
+      for (int nb = 0; nb < NT; ++nb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mine[(16 * mb + 4 * q + r) * RW + 16 * nb + l15] = acc[mb][nb][r];
+    __syncthreads();
+#pragma unroll 2
+    for (int e = tid; e < 16 * MT * 16 * NT; e += 256) {
+      const int ml = e / (16 * NT), nl = e - ml * (16 * NT);
+      const int m = m0 + ml, n = n0 + nl;
+      const float* s = red + ml * RW + nl;
+      const float v = (s[0] + s[RS]) + (s[2 * RS] + s[3 * RS]);
+      if (m >= p.M || n >= p.Ncol) continue;
+      float* dst;
+      if (p.R > 1) { const int co = m / p.R; dst = p.c + (long)co * p.Ncol * p.R + (m - co * p.R) + (long)n * p.R; }
+      else dst = p.c + (long)m * p.Ncol + n;
+      unsafeAtomicAdd(dst, v);
+    }
+    __syncthreads();                                 // (the next segment writes `red` again)
+#ifdef E2_DEBUG_ENV
+    ++nseg;
+#endif
+    rg.b += sg.n;
+  } while (rg.b < rg.e);
+#ifdef E2_DEBUG_ENV
+  // debug build (E2_PWKS_STAMPS): start, end and segment count of every work-group
+  if (p.stamps) {
+    __builtin_amdgcn_s_waitcnt(0);
+    KS_STAMP(6);
+    if (threadIdx.x == 0) p.stamps[8L * blockIdx.x + 7] = (unsigned long long)nseg;
+  }
+#endif
+}
+
+template <int MT, int NT, bool TAPS>
+int launch_ev(e2_ctx* ctx, const PgP& p, const WgEven& ev) {
+  const int lds = 4 * 16 * MT * (16 * NT + 4) * (int)sizeof(float);
+  static bool raised = false;                        // (one device per process: plan.py get_ctx)
+  if (!raised) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_wgrad_ev_kernel<MT, NT, TAPS>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) { e2_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return 1; }
+    raised = true;
+  }
+  PgP ps = p;
+#ifdef E2_DEBUG_ENV
+  // debug build: do the work-groups that flush twice (or more) set the kernel's duration?
+  const long grid = ev.G;
+  const bool stamps = e2_dbg_env("E2_PWKS_STAMPS") != nullptr && !ctx->capturing;
+  if (stamps) {
+    E2_CHECK_HIP(hipMalloc(&ps.stamps, sizeof(unsigned long long) * 8 * grid));
+    E2_CHECK_HIP(hipMemsetAsync(ps.stamps, 0, sizeof(unsigned long long) * 8 * grid, ctx->stream));
+  }
+#endif
+  hipLaunchKernelGGL((pw_wgrad_ev_kernel<MT, NT, TAPS>), dim3((unsigned)ev.G), dim3(256), lds, ctx->stream, ps, ev);
+  E2_CHECK_HIP(hipGetLastError());
+#ifdef E2_DEBUG_ENV
+  if (stamps) {
+    E2_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<unsigned long long> h(8 * grid);
+    E2_CHECK_HIP(hipMemcpy(h.data(), ps.stamps, sizeof(unsigned long long) * 8 * grid, hipMemcpyDeviceToHost));
+    unsigned long long t0 = ~0ull, t1 = 0;
+    double sum[2] = {0, 0}, mx[2] = {0, 0};
+    long cntw[2] = {0, 0};
+    for (long b = 0; b < grid; ++b) {
+      if (!h[8 * b + 6]) continue;                   // (empty work-groups)
+      const int k = h[8 * b + 7] > 1;
+      const double d = (double)(h[8 * b + 6] - h[8 * b]);
+      sum[k] += d; mx[k] = std::max(mx[k], d); ++cntw[k];
+      t0 = std::min(t0, h[8 * b]); t1 = std::max(t1, h[8 * b + 6]);
+    }
+    fprintf(stderr, "[e2] pw_wgrad_ev<%d,%d> G %d, %d tiles x %d units in %d bands, %d(+1 for %d) pairs each: first start -> last end %llu ticks\n",
+            MT, NT, ev.G, ev.T, ev.U, ev.B, ev.base, ev.extra, t1 - t0);
+    for (int k = 0; k < 2; ++k)
+      fprintf(stderr, "   %-22s %5ld work-groups, mean %9.0f max %9.0f ticks\n", k ? "two or more segments" : "one segment",
+              cntw[k], sum[k] / std::max(1L, cntw[k]), mx[k]);
+    (void)hipFree(ps.stamps);
+  }
+#endif
+  return 0;
+}
+
+// host side of both even forms: G work-groups over nMT * nNT tiles of p.steps units each, B bands
+static int even_split(const PgP& p, long G, int B, WgEven* ev) {
+  const long T = (long)p.nMT * p.nNT;
+  E2_REQUIRE(p.steps >= 1, "wgrad (even position ranges): no whole 32-position unit");
+  E2_REQUIRE(T * p.steps < (1L << 31), "wgrad (even position ranges): too many (tile, unit) pairs");
+  // what e2_last_launch reports is what runs: values out of range are refused, not clamped.  (B
+  // is the number of bands ASKED for; bands are whole rounds of four units, wgrad_even.hpp)
+  E2_REQUIRE(G >= 1 && G <= (1L << 16), "wgrad (even position ranges): %ld work-groups (1 .. 65536)", G);
+  E2_REQUIRE(B >= 1 && B <= p.steps, "wgrad (even position ranges): %d bands for %d units", B, p.steps);
+  *ev = wg_even_make((int)T, p.steps, (int)G, B);
+  return 0;
+}
+
 template <int MT, int NT, bool TAPS = false>
 int launch_ks(e2_ctx* ctx, const PgP& p, long grid) {
   const int lds = 4 * 16 * MT * (16 * NT + 4) * (int)sizeof(float);
@@ -441,8 +687,9 @@ int e2i_pw_wgrad(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S) {
   return 2;
 }
 
-// "MT,NT,8,0,S": the waves of a work-group split the positions (pw_wgrad_ks_kernel)
-int e2i_pw_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S) {
+// "MT,NT,8,0,S": the waves of a work-group split the positions (pw_wgrad_ks_kernel);
+// "MT,NT,8,B,G" (even = B >= 1): G work-groups with even position ranges in B bands (pw_wgrad_ev_kernel)
+int e2i_pw_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S, int even) {
   E2_REQUIRE(a.kd == 1 && a.kh == 1 && a.kw == 1, "pointwise wgrad: kernel %dx%dx%d is not 1x1x1", a.kd, a.kh, a.kw);
   E2_REQUIRE(a.xsY == a.Wo && a.xsZ == (int64_t)a.Ho * a.Wo && a.dsY == a.Wo && a.dsZ == (int64_t)a.Ho * a.Wo,
              "pointwise wgrad: x and dy need dense channel planes (row stride = W, plane stride = H * W)");
@@ -467,6 +714,7 @@ int e2i_pw_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S) {
   const long units = (long)a.N * p.stepsPerSample;
   E2_REQUIRE(units < (1L << 29), "pointwise wgrad: too many positions");
   p.steps = (int)units;
+  const long S0 = S;                                 // (even: the number of work-groups)
   S = (int)std::max<long>(1, std::min<long>(S, std::max<long>(1, (units + 3) / 4)));
   p.per = (int)std::max<long>(1, (units + S - 1) / S);
   p.per = (p.per + 3) & ~3;                          // whole rounds of the four waves
@@ -474,17 +722,20 @@ int e2i_pw_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S) {
   long grid = (long)p.nMT * p.nNT * p.S;
   grid = (grid + 7) & ~7L;                           // XCD-grouped order (the pad returns at once)
   E2_REQUIRE(grid < (1L << 31), "pointwise wgrad: grid too large");
+  WgEven ev{};
+  if (even > 0)
+    if (int rc = even_split(p, S0, even, &ev)) return rc;
   if (!a.accumulate)
     if (int rc = e2i_fill_flat(ctx, a.dw, (size_t)a.Cout * a.Cin, 0.f)) return rc;
-#define E2_L(M, N_) if (MT == M && NT == N_) return launch_ks<M, N_>(ctx, p, grid);
+#define E2_L(M, N_) if (MT == M && NT == N_) return even > 0 ? launch_ev<M, N_, false>(ctx, p, ev) : launch_ks<M, N_>(ctx, p, grid);
   E2_L(13, 2) E2_L(7, 2) E2_L(7, 4) E2_L(4, 4) E2_L(10, 2)
 #undef E2_L
   e2_set_error("pointwise wgrad (position-split waves): no instance MT=%d NT=%d", MT, NT);
   return 2;
 }
 
-// "MT,NT,9,0,S": the SAME kernel for a conv with taps (T = kd * kh * kw > 1).  dy lives in the
-// interior of its zero-padded buffer at the INPUT's row pitch (WgradArgs.dy_padded), so over the
+// "MT,NT,9,0,S" (and "MT,NT,9,B,G", B >= 1: even position ranges, pw_wgrad_ev_kernel): the SAME
+// kernel for a conv with taps (T = kd * kh * kw > 1).  dy lives in the interior of its zero-padded buffer at the INPUT's row pitch (WgradArgs.dy_padded), so over the
 // memory span of a plane -- K = (Ho - 1) * pitch + Wo positions, zeros in the kw - 1 gap columns
 // -- tap (tz, ty, tx) of input channel ci is the channel's plane read at the constant shift
 // tz * plane + ty * pitch + tx: every column (ci, tap) of dW (Cout x Cin * T, the weight tensor's
@@ -492,7 +743,7 @@ int e2i_pw_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S) {
 // Units are whole: one that runs past the end of its plane multiplies dy's zero border ((kh - 1)
 // rows >= 31 positions: required) with whatever x holds there -- the next plane / channel / sample,
 // or up to 124 bytes behind the tensor, which the caller vouches for (e2_set_input_slack).
-int e2i_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S) {
+int e2i_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S, int even) {
   const int T = a.kd * a.kh * a.kw;
   E2_REQUIRE(T > 1 && a.upR <= 1, "wgrad (position-split GEMM): a conv kernel with taps");
   E2_REQUIRE(a.dy_padded, "wgrad (position-split GEMM): dy must be the interior of its zero-padded buffer");
@@ -536,6 +787,7 @@ int e2i_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S) {
   const long units = (long)a.N * a.Do * p.stepsPerSample;
   E2_REQUIRE(units < (1L << 29), "wgrad (position-split GEMM): too many positions");
   p.steps = (int)units;
+  const long S0 = S;                                          // (even: the number of work-groups)
   S = (int)std::max<long>(1, std::min<long>(S, std::max<long>(1, (units + 3) / 4)));
   p.per = (int)std::max<long>(1, (units + S - 1) / S);
   p.per = (p.per + 3) & ~3;
@@ -543,9 +795,12 @@ int e2i_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S) {
   long grid = (long)p.nMT * p.nNT * p.S;
   grid = (grid + 7) & ~7L;
   E2_REQUIRE(grid < (1L << 31), "wgrad (position-split GEMM): grid too large");
+  WgEven ev{};
+  if (even > 0)
+    if (int rc = even_split(p, S0, even, &ev)) return rc;
   if (!a.accumulate)
     if (int rc = e2i_fill_flat(ctx, a.dw, (size_t)a.Cout * p.Ncol, 0.f)) return rc;
-#define E2_L(M, N_) if (MT == M && NT == N_) return launch_ks<M, N_, true>(ctx, p, grid);
+#define E2_L(M, N_) if (MT == M && NT == N_) return even > 0 ? launch_ev<M, N_, true>(ctx, p, ev) : launch_ks<M, N_, true>(ctx, p, grid);
   E2_L(13, 2) E2_L(7, 2) E2_L(7, 4) E2_L(4, 4) E2_L(10, 2) E2_L(5, 4) E2_L(3, 4) E2_L(2, 4) E2_L(8, 2) E2_L(8, 4) E2_L(6, 4)
 #undef E2_L
   e2_set_error("wgrad (position-split GEMM): no instance MT=%d NT=%d", MT, NT);

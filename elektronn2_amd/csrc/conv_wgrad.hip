@@ -573,10 +573,12 @@ int e2i_wgrad_conv(e2_ctx* ctx, const WgradArgs& a) {
   // WK 7 ("MT,NT,7,0,S"): 1x1x1 kernels -- the GEMM with K-contiguous operands (conv_pw_wgrad.hip)
   // WK 8 ("MT,NT,8,0,S"): the same GEMM, one 16 MT x 16 NT tile per work-group whose four waves split the positions
   if (c.WK == 7) return e2i_pw_wgrad(ctx, a, c.MT, c.NT, c.PS);
-  if (c.WK == 8) return e2i_pw_wgrad_ks(ctx, a, c.MT, c.NT, c.PS);
+  if (c.WK == 8) return e2i_pw_wgrad_ks(ctx, a, c.MT, c.NT, c.PS, c.BP);
+  // "MT,NT,8,B,G" / "MT,NT,9,B,G", B >= 1: the same tiles, G work-groups with EVEN position
+  // ranges in B bands (wgrad_even.hpp)
   // WK 9 ("MT,NT,9,0,S"): that GEMM for kernels WITH taps -- every (input channel, tap) column of dW is
   // a K-contiguous row of x at the tap's shift (needs the padded gradient at the input's row pitch)
-  if (c.WK == 9) return e2i_wgrad_ks(ctx, a, c.MT, c.NT, c.PS);
+  if (c.WK == 9) return e2i_wgrad_ks(ctx, a, c.MT, c.NT, c.PS, c.BP);
   if (a.dy_padded && (c.WK == 1 || c.WK == 14 || c.WK == 101 || c.WK == 114) && (c.BP == 128 || c.BP == 256))
     return e2i_wgrad_direct(ctx, a, c.MT, c.NT, c.BP, c.PS, (c.WK % 100) == 14 ? 4 : 1, c.WK >= 100);
   E2_REQUIRE(c.WK != 14 && c.WK < 100, "wgrad: WK=14/101/114 need the padded-gradient entry point and BP 128/256");

@@ -91,7 +91,7 @@ class Plan(object):
 
     def empty(self, shape):
         """an uninitialised tensor followed by SLACK zeros: the position-split weight gradient
-        (csrc/conv_pw_wgrad.hip, "MT,NT,9,0,S") reads up to 31 floats behind its input"""
+        (csrc/conv_pw_wgrad.hip, "MT,NT,9,0,S" and "MT,NT,9,B,G") reads up to 31 floats behind its input"""
         shape = tuple(int(s) for s in shape)
         n = int(np.prod(shape)) if shape else 1
         flat = torch.empty(n + self.SLACK, dtype=torch.float32, device=self.ctx.device)
