@@ -34,6 +34,8 @@ class E2Error(RuntimeError):
 
 # E2_POOL_* of include/e2hip.h (0 stays free for max)
 POOL_MODE = {'avg': 1, 'sum': 2}
+# E2_LRN_* of include/e2hip.h
+LRN_MODE = {'spatial': 0, 'channel': 1}
 
 
 class Tensor5(C.Structure):
@@ -162,6 +164,8 @@ def _load():
         "e2_maxpool3d_bwd": (C.c_int, [vp, P5, P5, i, i, i, P5, i]),
         "e2_pool3d_lin_fwd": (C.c_int, [vp, P5, i, i, i, i, i, i, i, P5]),
         "e2_pool3d_lin_bwd": (C.c_int, [vp, P5, i, i, i, i, i, i, i, P5, i]),
+        "e2_lrn_fwd": (C.c_int, [vp, P5, i, i, i, i, fp, fp, fp, P5, P5]),
+        "e2_lrn_bwd": (C.c_int, [vp, P5, P5, P5, i, i, i, i, fp, fp, P5, P5, i]),
         "e2_upconv3d_workspace_bytes": (sz, [i, i, i, i, i, i, i, i, i]),
         "e2_upconv3d_fwd": (C.c_int, [vp, P5, fp, fp, i, i, i, i, i, P5, vp, sz]),
         "e2_upconv3d_bwd": (C.c_int, [vp, P5, fp, P5, P5, i, i, i, i, P5, fp, fp, vp, sz]),
@@ -722,6 +726,24 @@ class Context:
                                     int(pool[2]), int(stride[0]), int(stride[1]), int(stride[2]),
                                     POOL_MODE.get(mode, mode), C.byref(t5(dx)),
                                     int(bool(accumulate))), "e2_pool3d_lin_bwd")
+
+    def lrn_fwd(self, x, mode, window, alpha, k, beta, out, q=None):
+        """out = x * (k + alpha * m)^(-beta), m the mean square over ``window`` = (fz, fx, fy)
+        around each element ('spatial', zeros outside) or over window[0] features ('channel', the
+        edge feature replicated); ``alpha`` / ``k`` / ``beta`` one-element device tensors the
+        kernel reads when it RUNS; ``q`` (None: not kept) receives k + alpha * m for lrn_bwd"""
+        _chk(_lib.e2_lrn_fwd(self.h, C.byref(t5(x)), LRN_MODE.get(mode, mode), int(window[0]),
+                             int(window[1]), int(window[2]), _fp(alpha), _fp(k), _fp(beta),
+                             C.byref(t5(q)) if q is not None else None, C.byref(t5(out))),
+             "e2_lrn_fwd")
+
+    def lrn_bwd(self, dout, x, q, mode, window, alpha, beta, tmp, dx, accumulate=False):
+        """dx (+)= the gradient of lrn_fwd: t = dout * x * q^(-beta-1) into ``tmp``, then a
+        gather over the window of t (two launches, no atomics)"""
+        _chk(_lib.e2_lrn_bwd(self.h, C.byref(t5(dout)), C.byref(t5(x)), C.byref(t5(q)),
+                             LRN_MODE.get(mode, mode), int(window[0]), int(window[1]),
+                             int(window[2]), _fp(alpha), _fp(beta), C.byref(t5(tmp)),
+                             C.byref(t5(dx)), int(bool(accumulate))), "e2_lrn_bwd")
 
     # ---- upconv ------------------------------------------------------------------
     def upconv_ws_bytes(self, cout, cin, pool, x_shape):

@@ -775,6 +775,15 @@ def modelload(file_name, model=None, override_mfp_to_active=False, imposed_patch
                     raise NotImplementedError(
                         "override_mfp_to_active: Pool node %r (mode %r) has no max-fragment-"
                         "pooling form; use predict_dense" % (n[0], mode))
+            if n[1] == 'LRN' and n[0] in keep:
+                # the channel mode is pointwise in space and acts on fragments as on the dense
+                # map; the spatial mode mixes neighbours behind a zero border -- neighbours of a
+                # fragment are not neighbours of the dense map
+                mode = n[2][2] if len(n[2]) > 2 else n[3].get('mode', 'spatial')
+                if mode == 'spatial':
+                    raise NotImplementedError(
+                        "override_mfp_to_active: LRN node %r (mode 'spatial') normalises over "
+                        "spatial neighbours, which max-fragment pooling separates" % (n[0],))
             if n[1] == 'Conv' and n[0] in keep:
                 n[3]['mfp'] = True
         dense_name = 'to_dense_' + pred[0]

@@ -8,6 +8,7 @@ bookkeeping (elektronn2/neuromancer/neural.py), executing through libe2hip.so.
   Pad       neural.py:1195-1279 constant frame (csrc/pad.hip)
   AutoMerge neural.py:1282-1407 (= UpConvMerge)
   Pool      neural.py:1409-1559 max (stride == pool); average / sum with any stride (csrc/pool.hip)
+  LRN       neural.py:2043-2181 local response normalisation, 'spatial' / 'channel' (csrc/lrn.hip)
 
   Perceptron neural.py:258-410  dot product (+ batch norm) -> +bias -> act  (config 1)
 
@@ -54,6 +55,15 @@ reference off cuDNN), ``mfp=True``, 1-D parents, other axis orders, an unknown m
 lists the modes); ``modelload(override_mfp_to_active=True)`` on a net whose prediction path holds a
 linear-mode Pool raises a NotImplementedError that names the node (there is no fragment form of it).
 
+Local response normalisation (``LRN(parent, filter_shape, mode='spatial', alpha, k, beta)``,
+neural.py:2043-2181): out = x / (k + alpha * m)^beta with m the mean square over a spatial box
+(zeros outside the tensor) or over neighbouring features (edge feature replicated); one launch
+forward, two backward (csrc/lrn.hip), f32 in either mfma mode.  The node is not a Conv: every fused
+route between two Convs tests ``type(...) is Conv`` on both ends (Conv._actbwd_into_parent,
+Conv._tail_gm, bf16_ahead's producer search) or on the child (Conv._fused_head, Conv._tail), so an
+LRN between two Convs keeps both on the launches that materialise the tensors it reads; the first
+writer of a Conv's gradient slabs is a Conv's data gradient alone, an LRN writes the plain gradient.
+
 Outside the hot path and therefore rejected with NotImplementedError here:
 gradnet, batch_normalisation='fadeout', the activations 'prelu', 'maxout <i>', 'concentration'
 and 'radius', 1-D convolutions.
@@ -73,7 +83,7 @@ from .variables import VariableWeight, ConstantParam, VariableParam
 logger = logging.getLogger('elektronn2log')
 
 __all__ = ['Conv', 'UpConv', 'Pool', 'Crop', 'Pad', 'AutoMerge', 'UpConvMerge', 'NeuralLayer',
-           'FragmentsToDense', 'Perceptron']
+           'FragmentsToDense', 'Perceptron', 'LRN']
 
 # fused into the pooling kernels / GEMM epilogues; and those that run through csrc/act.hip
 _PLAIN_ACTS = ('relu', 'lin', 'linear')
@@ -1620,3 +1630,121 @@ class Pool(Node):
         else:
             plan.ctx.pool_lin_bwd(plan.grad[self], self._p3, self._s3, lin, dst,
                                   accumulate=not first)
+
+
+class LRN(Node):
+    """Local response normalisation (neural.py:2043-2181)::
+
+        q = k + alpha * m          out = parent / q**beta
+
+    ``mode='spatial'``: ``filter_shape`` has one odd entry >= 1 per spatial axis ('b,f,z,x,y' with
+    three, 'b,f,x,y' / 'b,f,y,x' with two); m is the sum of parent**2 over that box around each
+    element inside its feature map, divided by the size of the box.  Positions outside the tensor
+    add 0 and the divisor stays the whole box: the reference's 'same' convolution of the squares
+    with an averaging filter that is the identity over the features (neural.py:2113-2118,
+    2148-2150).  That C x C x box ``average_filter`` constant is NOT materialised here and is not
+    among ``params``: the kernel sums the box.  An extent may exceed its axis.  An even extent
+    raises ValueError: the reference pads with Theano's 'half' mode, which returns ``in + 1``
+    positions there, while the node declares its parent's shape.
+
+    ``mode='channel'``: ``filter_shape`` is an odd int >= 1; m is the mean of parent**2 over that
+    many features around each one at the same position, indices clamped to the feature range (the
+    edge feature is replicated, neural.py:2152-2176).  Any 'b,f,...' parent with 2 or 3 spatial
+    axes.
+
+    ``alpha``, ``beta``, ``k`` are non-trainable parameters (``params``); the kernels read them
+    from device memory when they run, so ``set_value`` reaches a captured step without a new
+    capture.  Shape, strides, fov and offsets are the parent's.  Device side: csrc/lrn.hip, one
+    launch forward (which keeps q for a training plan), two backward; no gradient goes to the
+    three parameters.
+
+    Prediction-time rewrites: the channel mode is pointwise in space and passes through
+    ``predict_dense`` and ``modelload(override_mfp_to_active=True)``; the spatial mode keeps its
+    parent's fov yet mixes neighbours behind a zero border, which neither rewrite reproduces --
+    both raise a NotImplementedError that names the node."""
+
+    def __init__(self, parent, filter_shape, mode='spatial', alpha=0.0001, k=1, beta=0.75,
+                 name="LRN", print_repr=True):
+        super(LRN, self).__init__(parent, name, print_repr)
+        self.mode = mode
+        self.axis = parent.shape.tag2index('f')
+        tags = list(parent.shape.tags)
+        if mode == 'spatial':
+            self.spatial_axes = parent.shape.spatial_axes
+            conv_dim = len(self.spatial_axes)
+            try:
+                n_given = len(filter_shape)
+            except TypeError:
+                raise ValueError("LRN mode 'spatial': filter_shape must be a tuple with one "
+                                 "entry per spatial axis, not %r" % (filter_shape,))
+            if conv_dim != n_given:
+                raise ValueError("The filter_shape dimensionality (%i) and the number "
+                                 "of spatial dimensions in the input (%i)differ! "
+                                 "Use filter size 1 on axes which should not be "
+                                 "averaged." % (n_given, conv_dim))
+            if not ((conv_dim == 3 and tags == ['b', 'f', 'z', 'x', 'y'])
+                    or (conv_dim == 2 and tags in (['b', 'f', 'x', 'y'], ['b', 'f', 'y', 'x']))):
+                raise NotImplementedError("Cannot convolve non-standard shapes / axis orders. "
+                                          "Implement reshaping before conv"
+                                          "and re-reshaping afer!")
+            if not all(self._odd(f) for f in filter_shape):
+                raise ValueError("LRN filter_shape %r: every extent must be an odd int >= 1 (with "
+                                 "an even extent the reference's 'half' padding returns in + 1 "
+                                 "positions, not the parent's shape this node keeps)"
+                                 % (filter_shape,))
+            self.filter_shape = tuple(int(f) for f in filter_shape)
+            self.conv_dim = conv_dim
+            self._f3 = (1,) * (3 - conv_dim) + self.filter_shape
+        elif mode == 'channel':
+            if not self._odd(filter_shape):
+                raise ValueError("LRN mode 'channel': filter_shape must be an odd int >= 1, not %r"
+                                 % (filter_shape,))
+            n_sp = len(parent.shape.spatial_axes)
+            if not (tags[:2] == ['b', 'f'] and n_sp in (2, 3) and len(tags) == 2 + n_sp):
+                raise NotImplementedError("LRN mode 'channel' needs a 'b,f,...' parent with 2 or 3 "
+                                          "spatial axes, not %s" % (",".join(tags),))
+            self.filter_shape = int(filter_shape)
+            self._f3 = (self.filter_shape, 1, 1)
+        else:
+            raise ValueError("Unknow mode %s" % mode)
+        self.alpha = VariableParam(value=alpha, name="alpha", dtype=floatX, apply_train=False)
+        self.beta = VariableParam(value=beta, name="beta", dtype=floatX, apply_train=False)
+        self.k = VariableParam(value=k, name="k", dtype=floatX, apply_train=False)
+        self.params['alpha'] = self.alpha
+        self.params['beta'] = self.beta
+        self.params['k'] = self.k
+
+    @staticmethod
+    def _odd(f):
+        return isinstance(f, (int, np.integer)) and not isinstance(f, bool) and f >= 1 and f % 2 == 1
+
+    def _window_size(self):
+        return int(np.prod(self._f3))
+
+    def _calc_comp_cost(self):
+        self.computational_cost = self.parent.shape.stripnone_prod * self._window_size()
+
+    def _dev_params(self, plan):
+        return [plan.param(p).reshape(-1) for p in (self.alpha, self.k, self.beta)]
+
+    def _plan_alloc(self, plan):
+        plan.alloc_out(self)
+        if plan.training and plan.needs_grad(self.parent):
+            # what the backward reads next to x and the output gradient: q = k + alpha * m as the
+            # forward computed it, and room for t = dout * x * q^(-beta-1)
+            plan.scratch[self, 'q'] = plan.empty(plan.out_shape(self))
+            plan.scratch[self, 'tmp'] = plan.empty(plan.out_shape(self))
+
+    def _plan_fwd(self, plan):
+        alpha, k, beta = self._dev_params(plan)
+        plan.ctx.lrn_fwd(plan.out[self.parent], self.mode, self._f3, alpha, k, beta,
+                         plan.out[self], q=plan.scratch.get((self, 'q')))
+
+    def _plan_bwd(self, plan):
+        if not plan.needs_grad(self.parent):
+            return
+        dst, first = plan.grad_slot(self.parent)
+        alpha, k, beta = self._dev_params(plan)
+        plan.ctx.lrn_bwd(plan.grad[self], plan.out[self.parent], plan.scratch[self, 'q'], self.mode,
+                         self._f3, alpha, beta, plan.scratch[self, 'tmp'], dst,
+                         accumulate=not first)

@@ -400,6 +400,13 @@ class Node(object, metaclass=MetaNode):
                     "predict_dense: node %s (%s) pads its input: dense tiled prediction covers "
                     "valid nets only" % (n.name, "Pad" if type(n).__name__ == 'Pad'
                                          else "conv_mode=%r" % (n.conv_mode,)))
+            # a spatial LRN keeps its parent's fov yet mixes neighbours behind a zero border: the
+            # tiles' borders would not be the volume's (the channel mode is pointwise in space)
+            if type(n).__name__ == 'LRN' and n.mode == 'spatial':
+                raise NotImplementedError(
+                    "predict_dense: node %s (LRN, mode 'spatial') normalises over a zero-padded "
+                    "spatial window: dense tiled prediction does not reproduce the whole-volume "
+                    "result" % (n.name,))
         offset = np.asarray(self.shape.offsets)
         if np.any(offset < 0):
             raise ValueError("Cannot predict dense because the CNN contains "

@@ -315,6 +315,37 @@ int e2_pool3d_lin_fwd(e2_ctx*, const e2_tensor5* x, int pz, int py, int px, int 
 int e2_pool3d_lin_bwd(e2_ctx*, const e2_tensor5* dout, int pz, int py, int px, int sz, int sy,
                       int sx, int mode, const e2_tensor5* dx, int accumulate);
 
+/* ---- local response normalisation (neural.py:2043-2181 LRN node: 2113-2118 and 2148-2150 the
+ *      'spatial' mean square as a 'same' conv of x^2 with an identity-over-features averaging
+ *      filter, 2152-2176 the 'channel' one over the feature axis with a replicated edge,
+ *      2179-2180 the division) -----------------------------------------------------------------
+ * q = k + alpha * m, out = x * q^(-beta), m the mean square over a window:
+ *   SPATIAL  the box (fz, fy, fx) around the element inside its (n, c); positions outside the
+ *            tensor add 0 and the divisor is always fz fy fx.  The C x C x box filter of the
+ *            reference is never built.
+ *   CHANNEL  fz features around c at the same (n, z, y, x), indices clamped to [0, C - 1] (the
+ *            edge feature counts once per offset that lands on it); divisor fz; fy = fx = 1.
+ * Every extent is odd and >= 1 and may exceed its axis.  alpha, k, beta are DEVICE scalars read
+ * when the kernels run.  The forward is one launch and also writes q where q != NULL (the backward
+ * wants it).  Backward, with t = dout * x * q^(-beta-1) and N the divisor:
+ *   dx_i (+)= dout_i * q_i^(-beta) - (2 alpha beta / N) * x_i * sum_j mult(i, j) * t_j
+ * j over the same box, mult = 1 (SPATIAL); j over the features, mult(i, j) = the number of
+ * offsets o with clamp(j + o) == i (CHANNEL).  Two launches: t into `tmp` (same sizes as x), then
+ * a gather over the window of t -- no atomics, the same bits every run, windows walked in
+ * ascending (z, y, x) / feature order in f32; accumulate != 0 adds into dx (a plain read-add-
+ * write).  No gradient goes to alpha, k or beta; q <= 0 gives what powf gives.  All views
+ * arbitrary with identical sizes; nothing outside out / q / tmp / dx is written.  Errors: sizes
+ * that differ, an even or < 1 extent, another mode, a null pointer (q of the forward excepted),
+ * out aliasing x, dx aliasing dout (the windows read neighbours), tmp aliasing any other view, a
+ * channel of 2^31 elements or more. */
+enum { E2_LRN_SPATIAL = 0, E2_LRN_CHANNEL = 1 };
+int e2_lrn_fwd(e2_ctx*, const e2_tensor5* x, int mode, int fz, int fy, int fx,
+               const float* alpha, const float* k, const float* beta, const e2_tensor5* q,
+               const e2_tensor5* out);
+int e2_lrn_bwd(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* x, const e2_tensor5* q, int mode,
+               int fz, int fy, int fx, const float* alpha, const float* beta,
+               const e2_tensor5* tmp, const e2_tensor5* dx, int accumulate);
+
 /* ---- UpConv  (neural.py:989-1072; computations.py:216-255 upconv(),
  *      749-782 unpooling_nd; F2: y[n,co,p*i+r] = sum_ci w[co,ci,r] x[n,ci,i]) */
 /* (n,d,h,w) = dims of the UpConv INPUT x. */
