@@ -20,6 +20,7 @@ import json
 import math
 import os
 
+from . import tiling
 from .backend import E2Error
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -371,28 +372,30 @@ def force(kind, cfg):
         _forced.pop(kind, None)
 
 
+def _bf16(ctx):
+    return getattr(ctx, "mfma_dtype", "f32") == "bf16"
+
+
 def known(ctx, kind, sig):
     """the tiling tuned_call would run (kind, sig) with WITHOUT tuning: the pinned one, the
     table's entry, or None when the problem has not been tuned yet"""
     if kind in _forced:
         return _forced[kind]
-    suffix = "_bf16" if getattr(ctx, "mfma_dtype", "f32") == "bf16" else ""
-    key = "%s%s|%s" % (kind, suffix, ",".join(str(int(v)) for v in sig))
-    return _load().get(key)
+    return _load().get(tiling.key(kind, sig, _bf16(ctx)))
 
 
 def side_flag(ctx, sig):
     """f32 mode: does the weight gradient of problem ``sig`` (the 'wgrad' signature) run on the
     plan's side stream?  A measured, per-problem entry of the table like the tilings
     ("side|<sig>": "1"; tools/tune_side.py writes them, DESIGN finding 56)"""
-    if getattr(ctx, "mfma_dtype", "f32") == "bf16":
+    if _bf16(ctx):
         return False
-    return _load().get("side|" + ",".join(str(int(v)) for v in sig)) == "1"
+    return _load().get(tiling.side_key(sig)) == "1"
 
 
 def set_side_flag(sig, on):
     global _dirty
-    key = "side|" + ",".join(str(int(v)) for v in sig)
+    key = tiling.side_key(sig)
     c = _load()
     if on:
         c[key] = "1"
@@ -439,9 +442,7 @@ def tuned_call(ctx, kind, sig, cands, fn, allow_tune=True, fn_tune=None, fn_once
     Returns the tiling string used."""
     global _dirty
     ft = fn_tune if fn_tune is not None else fn
-    # the bf16 operand form of a kernel has its own best tiling
-    suffix = "_bf16" if getattr(ctx, "mfma_dtype", "f32") == "bf16" else ""
-    key = "%s%s|%s" % (kind, suffix, ",".join(str(int(v)) for v in sig))
+    key = tiling.key(kind, sig, _bf16(ctx))
     if kind in _forced:
         ctx.set_tiling(kind, _forced[kind])
         try:
@@ -501,7 +502,7 @@ def tuned_call(ctx, kind, sig, cands, fn, allow_tune=True, fn_tune=None, fn_once
                 for t, c in results:
                     if t > 1.015 * results[0][0]:
                         break
-                    if c and int(c.split(",")[2]) >= 100:
+                    if c and tiling.parse(kind, c).xcd_grouped:
                         best = c
                         break
             cache[key] = best

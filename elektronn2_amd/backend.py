@@ -17,7 +17,9 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
+from . import tiling
+
+_HERE =os.path.dirname(os.path.abspath(__file__))
 # E2HIP_LIB: explicit path of another build of the library (debug-switch / ablation builds
 # made by `make BUILD=... OUT=...`; the product build is never overwritten by experiments)
 LIB_PATH = os.environ.get("E2HIP_LIB") or os.path.join(_HERE, "libe2hip.so")
@@ -954,7 +956,7 @@ class Context:
                                        ws.numel() * ws.element_size()), "e2_conv3d_wgrad_bf16")
 
     def bf16_memory_wgrad(self):
-        return getattr(self, '_tiling', {}).get('wgrad', '').startswith('32,')
+        return tiling.is_memory_form('wgrad', self.current_tiling('wgrad'))
 
     def set_input_slack(self, nbytes):
         """promise (or, 0, withdraw the promise) that the x of the conv launches that follow has
@@ -967,12 +969,9 @@ class Context:
 
     # ---- the producers' epilogues: operands made ahead of the GEMM launches ------------------
     @staticmethod
-    def bf16_tile(tiling):
-        """(MB, NB) of a "32,MB,NB[,...]" tiling string, else None"""
-        v = (tiling or '').split(',')
-        if len(v) >= 3 and v[0] == '32':
-            return int(v[1]), int(v[2])
-        return None
+    def bf16_tile(s):
+        """(MB, NB) of a "32,MB,NB" tiling string, else None"""
+        return tiling.bf16_tile(s)
 
     @staticmethod
     def conv_bf16_wb_bytes(rows, kk, k, in_w, out_w, tile):
@@ -1120,7 +1119,7 @@ class Context:
         """True while the forced igemm tiling selects the kernel with bf16 operands in memory
         ("32,MB,NB", csrc/conv_bf16.hip): the callers that hold the canonical weights then
         call conv3d_fwd_bf16 / conv3d_dgrad_bf16 instead of the packed entry points"""
-        return getattr(self, '_tiling', {}).get('igemm', '').startswith('32,')
+        return tiling.is_memory_form('igemm', self.current_tiling('igemm'))
 
     def set_mfma_dtype(self, dtype):
         """'f32' (default) or 'bf16': operand rounding of the conv GEMMs (f32 sums)"""

@@ -20,8 +20,7 @@ activation) and of T.grad of that chain (model.py:182)."""
 import numpy as np
 import torch
 
-from .. import autotune, backend
-
+from .. import autotune, backend, tiling
 
 
 def _known(plan, kind, sig):
@@ -42,8 +41,7 @@ def conv_nodes(plan):
 def eligible(plan, node):
     """a Conv node that runs the generic conv path of the plan (not the fused first layer, the
     fused head or the tail), without batch normalisation / MFP, relu or lin"""
-    return (not node._fused_first(plan) and node._fused_head(plan) is None
-            and node._tail(plan) is None and not node._bn() and not node._mfp_pool()
+    return (node._route(plan) == 'gemm' and not node._bn() and not node._mfp_pool()
             and node._valid_mode()       # ('same' / 'full' read a framed image of their own)
             and node.activation_func in ('relu', 'lin')
             and tuple(node._p3) in node._PART_WINDOWS)
@@ -74,7 +72,7 @@ def prepare(plan):
                 if t is None:
                     return                    # (not tuned yet: after the first eager step)
                 tot += 1
-                mem += t.startswith('32,')
+                mem += tiling.is_memory_form(kind, t)
         if tot == 0 or mem < float(plan.opt['bf16_ahead_min']) * tot:
             plan._bf16_ahead_on = False
             return
@@ -93,7 +91,7 @@ def prepare(plan):
         # ---- forward ---------------------------------------------------------------------
         if (node, 'fwd') not in a:
             t = _known(plan, 'igemm', node._sig_fwd(plan))
-            tile = backend.Context.bf16_tile(t)
+            tile = tiling.bf16_tile(t)
             if tile is not None and plan.bf16_xkeep(node) is not None:
                 wb = _zeros_u8(plan, ctx.conv_bf16_wb_bytes(node.n_f, cin, k, x.shape[4], out.shape[4], tile))
                 a[node, 'fwd'] = dict(tile=t, wb=wb, job=(w5, 0, x.shape[4], out.shape[4], tile, wb))
@@ -108,7 +106,7 @@ def prepare(plan):
         want_d = plan.needs_grad(node.parent)
         if want_d and (node, 'dgrad') not in a:
             t = _known(plan, 'igemm', node._sig_dgrad(plan))
-            tile = backend.Context.bf16_tile(t)
+            tile = tiling.bf16_tile(t)
             if tile is not None:
                 wb = _zeros_u8(plan, ctx.conv_bf16_wb_bytes(cin, node.n_f, k, dyp.shape[4], x.shape[4], tile))
                 kg = (node.n_f + 15) // 16 * 2
@@ -120,7 +118,7 @@ def prepare(plan):
         # ---- weight gradient ---------------------------------------------------------------
         if (node, 'wgrad') not in a:
             t = _known(plan, 'wgrad', node._sig_wgrad(plan))
-            if t and t.startswith('32,'):
+            if tiling.is_memory_form('wgrad', t):
                 plane, dbytes, sbytes = ctx.wgrad_bf16_geometry(x.shape, node.n_f, k)
                 a[node, 'wgrad'] = dict(tile=t, dyc=_zeros_u8(plan, dbytes),
                                         sums=torch.zeros(sbytes // 4, device=ctx.device),

@@ -611,26 +611,34 @@ class Conv(NeuralLayer):
         nbytes = 4 * int(np.prod(shape))
         return 8 if 8 * nbytes <= (512 << 20) else 1
 
+    def _route(self, plan):
+        """the launches that run this node: 'head' (csrc/head.hip), 'first' (csrc/conv_first.hip),
+        'tail' (csrc/tail.hip) or 'gemm' (the conv GEMMs and the passes around them)"""
+        key = (self, 'route')
+        if key not in plan.scratch:
+            plan.scratch[key] = ('head' if self._fused_head(plan) is not None else
+                                 'first' if self._fused_first(plan) else
+                                 'tail' if self._tail(plan) is not None else 'gemm')
+        return plan.scratch[key]
+
     def _plan_alloc(self, plan):
         N = plan.out_shape(self.parent)[0]     # (the fragments of MFP sit on the batch axis)
         psp = self._sp3(self.parent.shape)
-        k = self._k3
         if not self._valid_mode():
             plan.framed_input(self)            # (scratch 'xf': every launch below reads it as x)
             psp = self._x_shape(plan)[2:]
         if self.mfp and plan.training:
             raise NotImplementedError("MFP is a prediction-time rewrite of the net "
                                       "(neural.py:531-533); train without it")
-        if self._fused_head(plan) is not None:
+        route = self._route(plan)
+        if route == 'head':
             plan.out[self] = None             # the logits are never materialised
-            return
-        if self._fused_first(plan):
+        elif route == 'first':
             plan.alloc_out(self)
             if plan.training:
-                nb = plan.ctx.conv1_bwd_ws_bytes(plan.out_shape(self), k)
+                nb = plan.ctx.conv1_bwd_ws_bytes(plan.out_shape(self), self._k3)
                 plan.scratch[self, 'ws1'] = plan.empty_flat(nb // 4 + 16)
-            return
-        if self._tail(plan) is not None:
+        elif route == 'tail':
             # neither the activations nor their gradient are materialised; what the launch
             # leaves behind is `dy` (the pre-activation's gradient: this layer's weight
             # gradient reads it, 128 B of slack behind it as for any padded gradient) and the
@@ -638,7 +646,7 @@ class Conv(NeuralLayer):
             head = self._tail(plan)[0]
             plan.out[self] = None
             cin = self.parent.shape['f']
-            nb = plan.ctx.conv_ws_bytes(self.n_f, cin, k)
+            nb = plan.ctx.conv_ws_bytes(self.n_f, cin, self._k3)
             plan.scratch[self, 'wp_f'] = plan.zeros_flat(nb // 4 + 64)
             plan.pack_jobs.append((self.w, plan.scratch[self, 'wp_f'], 0))
             ysh = (N, self.n_f) + tuple(psp)
@@ -650,7 +658,11 @@ class Conv(NeuralLayer):
                 plan.pack_jobs.append((self.w, plan.scratch[self, 'wp_d'], 1))
             wsb = plan.ctx.tail_ws_bytes(plan.out_shape(self.parent), self.n_f, head.n_f)
             plan.scratch[self, 'tail_ws'] = plan.empty_flat(wsb // 4 + 16)
-            return
+        else:
+            self._alloc_gemm(plan, N, psp)
+
+    def _alloc_gemm(self, plan, N, psp):
+        k = self._k3
         osp = [psp[i] - k[i] + 1 for i in range(3)]
         if not self._fused_act(plan):
             ysh = (N, self.n_f) + tuple(osp)
@@ -708,13 +720,13 @@ class Conv(NeuralLayer):
                 plan.pack_jobs.append((self.w, plan.scratch[self, 'wp_d'], 1))
                 plan.pack_nodes[id(plan.scratch[self, 'wp_d'])] = (self, 1)
 
-    # ---- the tuning keys of the node's three GEMM launches --------------------------------
+    # ---- the tuning keys of the node's three GEMM launches: what the launches run under AND what
+    # every lookup asks for (Plan._refine_pack_rows, Plan.side_forced, bf16_ahead.prepare) -------
     def _sig_fwd(self, plan):
-        x = self._x(plan)
-        cin = self.parent.shape['f']
-        if self._fused_act(plan):
-            return (2, self.n_f, cin) + tuple(self._k3) + tuple(plan.out[self].shape[2:]) + (x.stride(3),)
-        return (0, self.n_f, cin) + tuple(self._k3) + tuple(plan.scratch[self, 'y'].shape[2:]) + (x.stride(3),)
+        fused = self._fused_act(plan)
+        osp = (plan.out[self] if fused else plan.scratch[self, 'y']).shape[2:]
+        return (2 if fused else 0, self.n_f, self.parent.shape['f']) + tuple(self._k3) + tuple(osp) + \
+            (self._x(plan).stride(3),)
 
     def _sig_dgrad(self, plan):
         dst = plan.grad[self.parent]
@@ -737,6 +749,21 @@ class Conv(NeuralLayer):
         x, dy = self._x(plan), plan.scratch[self, 'dy']
         return (self.n_f, self.parent.shape['f']) + tuple(self._k3) + tuple(dy.shape[2:]) + \
             (x.stride(3), dy.stride(3))
+
+    def _candidates(self, plan, which):
+        """the tilings the tuner is offered for the launch with the key _sig_<which>; 'dgrad_act': the
+        data gradient that carries the parent's activation backward (no form with bf16 operands in
+        memory).  Launch sites only: a lookup does not pay for building hundreds of strings."""
+        n_f, cin, k = self.n_f, self.parent.shape['f'], self._k3
+        if which == 'wgrad':
+            return autotune.wgrad_candidates(n_f, cin, k, plan.scratch[self, 'dy'].shape[2:]) + \
+                plan.bf16_wgrad_cands(cin, k)
+        if which == 'fwd':
+            fused = self._fused_act(plan)          # (the fused epilogue cannot split K)
+            osp = (plan.out[self] if fused else plan.scratch[self, 'y']).shape[2:]
+            return autotune.igemm_candidates(n_f, cin, k, osp, split_k=not fused) + plan.bf16_cands(cin)
+        c = autotune.igemm_candidates(cin, n_f, k, plan.grad[self.parent].shape[2:])
+        return c if which == 'dgrad_act' else c + plan.bf16_cands(n_f)
 
     def _need_f32_dy(self, plan):
         """a launch is about to read the f32 gradient of the pre-activation: it must exist"""
@@ -765,15 +792,15 @@ class Conv(NeuralLayer):
             plan._xb_ready[nx[2]] = True
 
     def _plan_fwd(self, plan):
-        ctx = plan.ctx
-        if self._fused_head(plan) is not None:
+        ctx, route = plan.ctx, self._route(plan)
+        if route == 'head':
             return                            # done by the Softmax / NLL node
         x = self._x(plan)
         if plan.scratch.get((self, 'xf_launch')):
             # the framed image by one launch (the in-place route has none: the parent's producing
             # launch wrote the interior, the frame is zero since the plan was built)
             ctx.pad5(plan.out[self.parent], x, self._q3)
-        if self._fused_first(plan):
+        if route == 'first':
             nx = bf16_ahead.next_image(plan, self)
             if nx is not None:            # bf16 mode: + the next conv's channels-last input image
                 ctx.conv1_pool_act_fwd_bf16(x, self._w5(plan.param(self.w)), plan.param(self.b),
@@ -782,16 +809,20 @@ class Conv(NeuralLayer):
             else:
                 ctx.conv1_pool_act_fwd(x, self._w5(plan.param(self.w)), plan.param(self.b), self._p3,
                                        self.activation_func, plan.out[self])
-            return
-        if self._tail(plan) is not None:
-            return                            # done by the NLL node (csrc/tail.hip)
+        elif route == 'gemm':                 # ('tail': done by the NLL node, csrc/tail.hip)
+            y_nparts = self._fwd_gemm(plan, x)
+            if not self._fused_act(plan):
+                self._fwd_post(plan, y_nparts)
+
+    def _fwd_gemm(self, plan, x):
+        """the forward GEMM: with bias + activation in its epilogue into the output (_fused_act), or
+        into the pre-activation `y` / its split-K slabs; returns the parts the (last) launch wrote"""
+        ctx = plan.ctx
         wp = plan.scratch[self, 'wp_f']       # packed by the plan's multi-pack launch
         plan.join_side()                      # ... which runs on the side stream
-        cin = self.parent.shape['f']
         if self._fused_act(plan):
             out = plan.out[self]
-            sig = (2, self.n_f, cin) + tuple(self._k3) + tuple(out.shape[2:]) + \
-                (x.stride(3),)
+
             def fwd_act():
                 if ctx.bf16_memory_form():
                     self._bf16_fwd(plan, x, out, bias=plan.param(self.b), act=self.activation_func)
@@ -801,15 +832,9 @@ class Conv(NeuralLayer):
                     with plan.image(wp):
                         ctx.conv3d_fwd_packed_act(x, wp, self.n_f, self._k3, plan.param(self.b),
                                                   self.activation_func, out)
-            plan.tuned('igemm', sig,
-                       autotune.igemm_candidates(self.n_f, cin, self._k3,
-                                                 out.shape[2:], split_k=False) +
-                       plan.bf16_cands(cin), fwd_act)
-            return
-        y = plan.scratch[self, 'y']
-        sig = (0, self.n_f, cin) + tuple(self._k3) + tuple(y.shape[2:]) + \
-            (x.stride(3),)
-        yp = plan.scratch[self, 'y_parts']
+            plan.tuned('igemm', self._sig_fwd(plan), self._candidates(plan, 'fwd'), fwd_act)
+            return 1
+        y, yp = plan.scratch[self, 'y'], plan.scratch[self, 'y_parts']
         got = [1]                              # parts the (last) launch wrote
 
         def fwd_plain():
@@ -823,10 +848,12 @@ class Conv(NeuralLayer):
             else:
                 with plan.image(wp):
                     ctx.conv3d_fwd_packed(x, wp, self.n_f, self._k3, y)
-        plan.tuned('igemm', sig,
-                   autotune.igemm_candidates(self.n_f, cin, self._k3, y.shape[2:]) +
-                   plan.bf16_cands(cin), fwd_plain, out=y)
-        y_nparts = got[0]
+        plan.tuned('igemm', self._sig_fwd(plan), self._candidates(plan, 'fwd'), fwd_plain, out=y)
+        return got[0]
+
+    def _fwd_post(self, plan, y_nparts):
+        """the pass behind the forward GEMM, from `y` (or `y_nparts` partial sums) to the node's output"""
+        ctx, y, yp = plan.ctx, plan.scratch[self, 'y'], plan.scratch[self, 'y_parts']
         if self._bn():
             lin = y
             if any(p != 1 for p in self._p3):
@@ -884,29 +911,39 @@ class Conv(NeuralLayer):
                                   plan.out[self])
 
     def _plan_bwd(self, plan):
-        ctx = plan.ctx
-        if self._fused_head(plan) is not None:
+        route = self._route(plan)
+        if route == 'head':
             return
         x = self._x(plan)
-        if self._fused_first(plan):
+        if route == 'first':
             if plan.opt['side_join_first']:
                 # (the last launch of the backward chain: next to the side stream's weight
                 # gradients it shares the CUs and takes 1.8x its time; behind them it runs alone)
                 plan.join_side()
-            ctx.conv1_pool_act_bwd(x, self._w5(plan.param(self.w)), plan.param(self.b), plan.grad[self],
-                                   self._p3, self.activation_func, plan.pgrad(self.w),
-                                   plan.pgrad(self.b), ws=plan.scratch[self, 'ws1'])
+            plan.ctx.conv1_pool_act_bwd(x, self._w5(plan.param(self.w)), plan.param(self.b), plan.grad[self],
+                                        self._p3, self.activation_func, plan.pgrad(self.w),
+                                        plan.pgrad(self.b), ws=plan.scratch[self, 'ws1'])
             return
-        dy = plan.scratch[self, 'dy']
-        tail = self._tail(plan) is not None
-        if tail:
+        if route == 'tail':
             # the tail launch wrote dy, the parent's output gradient (first and only writer)
             # and the slots the NLL node's reduction has added into the bias gradient
             if plan.needs_grad(self.parent):
                 plan.grad_slot(self.parent)
                 if self._tail_gm(plan) is not None:    # ... through its activation backward
                     plan.scratch[self.parent, 'dy_by_tail'] = True
-        elif self._bn():
+        else:
+            self._bwd_dy(plan)
+        self._bwd_wgrad(plan, x)
+        if plan.needs_grad(self.parent) and route != 'tail':
+            if self._actbwd_into_parent(plan):
+                self._bwd_dgrad_actbwd(plan)
+            else:
+                self._bwd_dgrad(plan)
+
+    def _bwd_dy(self, plan):
+        """`dy`, the pre-activation's gradient, from the output gradient (unless another launch wrote it)"""
+        ctx, dy = plan.ctx, plan.scratch[self, 'dy']
+        if self._bn():
             train = self.batch_normalisation == 'train'
             pooled = any(p != 1 for p in self._p3)
             lin = plan.scratch[self, 'lin'] if pooled else plan.scratch[self, 'y']
@@ -968,13 +1005,13 @@ class Conv(NeuralLayer):
                 ctx.pool_bias_act_bwd(plan.grad[self], plan.scratch[self, 'y'],
                                       plan.param(self.b), self._p3, self.activation_func, dy,
                                       plan.pgrad(self.b))
-        cin = self.parent.shape['f']
+
+    def _bwd_wgrad(self, plan, x):
+        """the weight-gradient launch, on the side stream"""
+        ctx, dy, dyp = plan.ctx, plan.scratch[self, 'dy'], plan.scratch[self, 'dy_pad']
         dw = self._w5(plan.pgrad(self.w))
-        dyp = plan.scratch[self, 'dy_pad']
-        sigw = (self.n_f, cin) + tuple(self._k3) + tuple(dy.shape[2:]) + \
-            (x.stride(3), dy.stride(3))
-        wcands = plan.bf16_wgrad_cands(cin, self._k3)
-        wws = plan.bf16_wgrad_ws(self) if wcands else None
+        sig = self._sig_wgrad(plan)
+        wws =plan.bf16_wgrad_ws(self) if plan.bf16_wgrad_cands(self.parent.shape['f'], self._k3) else None
 
         def wgrad(accumulate):
             if ctx.bf16_memory_wgrad():     # "32,MB,NB,0,S": bf16 operands in memory
@@ -1000,90 +1037,84 @@ class Conv(NeuralLayer):
         def wgrad_launch():
             ctx.set_input_slack(slack)
             try:
-                plan.tuned('wgrad', sigw,
-                           autotune.wgrad_candidates(self.n_f, cin, self._k3, dy.shape[2:]) + wcands,
+                plan.tuned('wgrad', sig, self._candidates(plan, 'wgrad'),
                            lambda: wgrad(True), fn_tune=lambda: wgrad(False))
             finally:
                 ctx.set_input_slack(0)
         plan.on_side(wgrad_launch, defer=True, force=plan.side_forced(self))
-        if plan.needs_grad(self.parent) and not tail:
-            wp = plan.scratch[self, 'wp_d']
-            dyp = plan.scratch[self, 'dy_pad']
-            par = self.parent
-            if self._actbwd_into_parent(plan):
-                # the parent conv does not pool and feeds only this conv: its activation
-                # backward runs in this launch's epilogue, which writes the parent's
-                # zero-padded gradient buffer and bias gradient directly
-                pdyp = plan.scratch[par, 'dy_pad']
-                ppad = [kk - 1 for kk in par._k3]
-                if par._fused_act(plan):
-                    src, pb = plan.out[par], None
-                else:
-                    src, pb = plan.scratch[par, 'y'], plan.param(par.b)
-                osp = plan.out_shape(par)[2:]
-                sig = (1, cin, self.n_f) + tuple(self._k3) + tuple(osp) + \
-                    (dyp.stride(3),)
-                plan._grad_written.add(id(par))
-                plan.scratch[par, 'dy_done'] = True
 
-                def launch(dbias):
-                    with plan.image(wp):
-                        ctx.conv3d_dgrad_packed_actbwd(dyp, wp, cin, self._k3, src,
-                                                       par.activation_func, pdyp, ppad, dbias,
-                                                       bias_prev=pb)
-                plan.tuned('igemm', sig,
-                           autotune.igemm_candidates(cin, self.n_f, self._k3, osp),
-                           lambda: launch(plan.pgrad(par.b)), fn_tune=lambda: launch(None),
-                           fn_once=lambda: launch(plan.pgrad(par.b)), out=pdyp)
-                return
-            dst, first = plan.grad_slot(self.parent)
-            out = dst if first else plan.tmp_like(dst)
-            # first writer of the parent's output gradient: split-K partial sums go to the
-            # parent's slabs, its activation backward adds them up
-            gparts = plan.scratch.get((self.parent, 'grad_parts')) if first else None
-            got = [1]
-            sig = (1, cin, self.n_f) + tuple(self._k3) + tuple(out.shape[2:]) + \
-                (dyp.stride(3),)
-            dyi = self._dy_inset(plan)         # ('same' / 'full': the interior's gradient only)
-            zin = self._q3[0]
+    def _bwd_dgrad_actbwd(self, plan):
+        """the parent conv does not pool and feeds only this conv (_actbwd_into_parent): its
+        activation backward runs in this data-gradient launch's epilogue, which writes the parent's
+        zero-padded gradient buffer and bias gradient directly"""
+        ctx, par, cin = plan.ctx, self.parent, self.parent.shape['f']
+        wp, dyp = plan.scratch[self, 'wp_d'], plan.scratch[self, 'dy_pad']
+        pdyp = plan.scratch[par, 'dy_pad']
+        ppad = [kk - 1 for kk in par._k3]
+        if par._fused_act(plan):
+            src, pb = plan.out[par], None
+        else:
+            src, pb = plan.scratch[par, 'y'], plan.param(par.b)
+        plan._grad_written.add(id(par))
+        plan.scratch[par, 'dy_done'] = True
 
-            def dgrad():
-                if zin:                        # (the z border the launch may skip is thinner)
-                    ctx.set_dgrad_zinset(zin)
-                try:
-                    dgrad_launch()
-                finally:
-                    if zin:
-                        ctx.set_dgrad_zinset(0)
+        def launch(dbias):
+            with plan.image(wp):
+                ctx.conv3d_dgrad_packed_actbwd(dyp, wp, cin, self._k3, src,
+                                               par.activation_func, pdyp, ppad, dbias,
+                                               bias_prev=pb)
+        plan.tuned('igemm', self._sig_dgrad(plan), self._candidates(plan, 'dgrad_act'),
+                   lambda: launch(plan.pgrad(par.b)), fn_tune=lambda: launch(None),
+                   fn_once=lambda: launch(plan.pgrad(par.b)), out=pdyp)
 
-            def dgrad_launch():
-                if ctx.bf16_memory_form():
-                    ad = plan.bf16a.get((self, 'dgrad'))
-                    if ad is not None and plan._dy_ready.get(self) and ad['tile'] == ctx.current_tiling('igemm'):
-                        plan.ensure_wb()
-                        ctx.conv3d_dgrad_bf16_ex(dyi, self._w5(plan.param(self.w)), out,
-                                                 ws=plan.bf16_ws(self), dy_cl=ad['cl'],
-                                                 wb=ad['wb'] if plan._wb_ready else None)
-                    else:
-                        self._need_f32_dy(plan)
-                        ctx.conv3d_dgrad_bf16(dyi, self._w5(plan.param(self.w)), out,
-                                              ws=plan.bf16_ws(self))
-                    got[0] = 1
-                elif gparts is not None:
-                    self._need_f32_dy(plan)
-                    with plan.image(wp):
-                        got[0] = ctx.conv3d_dgrad_packed_parts(dyi, wp, cin, self._k3, gparts)
+    def _bwd_dgrad(self, plan):
+        """the data-gradient launch into (or, a later writer, onto) the parent's output gradient"""
+        ctx, cin = plan.ctx, self.parent.shape['f']
+        wp = plan.scratch[self, 'wp_d']
+        dst, first = plan.grad_slot(self.parent)
+        out = dst if first else plan.tmp_like(dst)
+        # first writer of the parent's output gradient: split-K partial sums go to the
+        # parent's slabs, its activation backward adds them up
+        gparts = plan.scratch.get((self.parent, 'grad_parts')) if first else None
+        got = [1]
+        dyi = self._dy_inset(plan)         # ('same' / 'full': the interior's gradient only)
+        zin = self._q3[0]
+
+        def dgrad():
+            if zin:                        # (the z border the launch may skip is thinner)
+                ctx.set_dgrad_zinset(zin)
+            try:
+                dgrad_launch()
+            finally:
+                if zin:
+                    ctx.set_dgrad_zinset(0)
+
+        def dgrad_launch():
+            if ctx.bf16_memory_form():
+                ad = plan.bf16a.get((self, 'dgrad'))
+                if ad is not None and plan._dy_ready.get(self) and ad['tile'] == ctx.current_tiling('igemm'):
+                    plan.ensure_wb()
+                    ctx.conv3d_dgrad_bf16_ex(dyi, self._w5(plan.param(self.w)), out,
+                                             ws=plan.bf16_ws(self), dy_cl=ad['cl'],
+                                             wb=ad['wb'] if plan._wb_ready else None)
                 else:
                     self._need_f32_dy(plan)
-                    with plan.image(wp):
-                        ctx.conv3d_dgrad_packed(dyi, wp, cin, self._k3, out)
-            plan.tuned('igemm', sig,
-                       autotune.igemm_candidates(cin, self.n_f, self._k3, out.shape[2:]) +
-                       plan.bf16_cands(self.n_f), dgrad, out=out)
-            if first:
-                plan.scratch[self.parent, 'grad_nparts'] = got[0]
-            if not first:
-                ctx.copy5(out, dst, accumulate=True)
+                    ctx.conv3d_dgrad_bf16(dyi, self._w5(plan.param(self.w)), out,
+                                          ws=plan.bf16_ws(self))
+                got[0] = 1
+            elif gparts is not None:
+                self._need_f32_dy(plan)
+                with plan.image(wp):
+                    got[0] = ctx.conv3d_dgrad_packed_parts(dyi, wp, cin, self._k3, gparts)
+            else:
+                self._need_f32_dy(plan)
+                with plan.image(wp):
+                    ctx.conv3d_dgrad_packed(dyi, wp, cin, self._k3, out)
+        plan.tuned('igemm', self._sig_dgrad(plan), self._candidates(plan, 'dgrad'), dgrad, out=out)
+        if first:
+            plan.scratch[self.parent, 'grad_nparts'] = got[0]
+        if not first:
+            ctx.copy5(out, dst, accumulate=True)
 
     def _actbwd_into_parent(self, plan):
         """this conv's data gradient can carry the activation backward of its parent: the

@@ -637,30 +637,6 @@ class Plan(object):
                     plan.ctx.set_image_rows(0)
         return _I()
 
-    @staticmethod
-    def _tile_rows(tiling, m):
-        """how far the M tiles of a conv GEMM launch with this tiling string reach for m output
-        rows, or 0 (= the repack's default) when the string is unknown / of another kernel family"""
-        if not tiling:
-            return 0
-        try:
-            v = [int(t) for t in tiling.split(",")]
-        except ValueError:
-            return 0
-        if len(v) == 4:                                   # "MT,NT,CC,SK": 16x16x4 kernel
-            per = 16 * v[0]
-        elif len(v) == 8 and v[0] == 4:                   # "4,MG,NT,CC,SK,WM,WN,G": 4x4x1 kernel
-            per = 4 * v[1] * v[5]
-        elif len(v) in (3, 5) and v[0] == 1:              # "1,MT,NT[,KC,0]": pointwise GEMM
-            per = 16 * v[1]
-        elif v[0] == 32:                                  # bf16 operands in memory: image not read
-            per = 16
-        else:
-            return 0
-        # (whole 128-byte lines: a line the repack writes only in part is merged with memory when the
-        # GEMM fetches it -- rows cut at 80 made the 5 x 2 tiles 6 % slower)
-        return -(-(-(-m // per) * per) // 32) * 32
-
     def _refine_pack_rows(self):
         """after the first eager step the tiling of every conv launch is known (tuned or from the
         shipped table): the repack then rewrites, per image, only the padding rows THAT tiling
@@ -671,7 +647,7 @@ class Plan(object):
         want_rows, want_stride = self.opt['pack_rows'], self.opt['image_stride'] and self._upd is None
         if not (want_rows or want_stride) or self._pack_dev is None:
             return
-        from .. import autotune
+        from .. import autotune, tiling
         rows, strides, any_ = [], [], False
         self._img_stride = {}
         for (w, wp, mode) in self.pack_jobs:
@@ -686,14 +662,9 @@ class Plan(object):
                         t, m = autotune.known(self.ctx, 'igemm', node._sig_dgrad(self)), node.parent.shape['f']
                     else:
                         t, m = None, 0
-                    r = self._tile_rows(t, m)
-                    # a row length of its own only for the 16x16x4 / pointwise kernels (the 4x4x1
-                    # kernel's lanes read 64 consecutive floats per row; a memory-form tiling does
-                    # not read the image, but the launch that replaces it under another pin would)
-                    v = [int(q) for q in t.split(",")] if t else []
-                    # (measured for the 4x4x1 kernel too -- rows of 64 floats for 20 channels --:
-                    # neuro3d_lite +5 us, neuro3d -5 us, not of one sign: its images keep the formula)
-                    if want_stride and r and (len(v) == 4 or (len(v) in (3, 5) and v[0] == 1)):
+                    t = tiling.parse('igemm', t)
+                    r = tiling.rows_reached(t, m)
+                    if want_stride and r and tiling.own_row_length(t):
                         # exactly as long as the tiles reach: measured against + 16 floats and against
                         # rows rounded to whole 128-byte lines, the densest form wins (finding 52)
                         st = -(-max(r, -(-m // 16) * 16) // 16) * 16
