@@ -121,11 +121,14 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(V5 x, const float* __re
     sd = run_std[c];
   }
   if (threadIdx.x == 0 && save) { save[c] = mean; save[x.c + c] = sd; }
+  // (gamma / std) x + b - gamma mean / std as a (x - mean) + b: the two large terms of the literal
+  // form cancel where std is tiny (a constant channel: std = 1e-6, both terms ~1e6 |x|, and the
+  // result, b, was lost in their rounding); here x - mean is exact there and the output is act(b)
   const float a = gamma[c] / sd;
-  const float b = bias[c] - gamma[c] * mean / sd;
+  const float b = bias[c];
   for (int n = 0; n < x.n; ++n)
     for (unsigned s = threadIdx.x; s < S; s += 256) {
-      float v = a * x.p[elem_off(x, n, c, s)] + b;
+      float v = a * (x.p[elem_off(x, n, c, s)] - mean) + b;
       if (act == E2_ACT_RELU) v = fmaxf(v, 0.f);
       out.p[elem_off(out, n, c, s)] = v;
     }
@@ -147,14 +150,14 @@ __global__ __launch_bounds__(256) void bn_act_bwd_kernel(V5 dout, V5 x, const fl
   const long cnt = (long)x.n * S;
   const float mean = save[c], sd = save[x.c + c];
   const float g = gamma[c];
-  const float a = g / sd, b = bias[c] - g * mean / sd;
+  const float a = g / sd, b = bias[c];
   float s1 = 0.f, s2 = 0.f;
   for (int n = 0; n < x.n; ++n)
     for (unsigned s = threadIdx.x; s < S; s += 256) {
       const float xv = x.p[elem_off(x, n, c, s)];
       float d = dout.p[elem_off(dout, n, c, s)];
       if (act == E2_ACT_RELU) {
-        const float pre = a * xv + b;
+        const float pre = a * (xv - mean) + b;        // as the forward computed it
         d *= (pre > 0.f) ? 1.f : ((pre == 0.f) ? 0.5f : 0.f);
       }
       s1 += d;
@@ -175,7 +178,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_kernel(V5 dout, V5 x, const fl
       const float xv = x.p[elem_off(x, n, c, s)];
       float d = dout.p[elem_off(dout, n, c, s)];
       if (act == E2_ACT_RELU) {
-        const float pre = a * xv + b;
+        const float pre = a * (xv - mean) + b;        // as the forward computed it
         d *= (pre > 0.f) ? 1.f : ((pre == 0.f) ? 0.5f : 0.f);
       }
       dx.p[elem_off(dx, n, c, s)] = a * (d - m_d - ((xv - mean) / sd) * m_dx);

@@ -1345,6 +1345,13 @@ class UpConv(Conv):
             # not); the backward takes the slope from it -- not from the output, as the relu
             # form does, which cannot tell the sign of abs's argument
             plan.scratch[self, 'pre'] = plan.empty(plan.out_shape(self))
+        if self._bn():
+            # batch norm acts on the bare upconvolution (neural.py:1032-1061): the GEMM leaves it
+            # in `lin`, e2_batchnorm_act_fwd carries it to the output (or to `pre`)
+            plan.scratch[self, 'lin'] = plan.empty(plan.out_shape(self))
+            plan.scratch[self, 'bn_save'] = plan.zeros_flat(2 * self.n_f)
+            if plan.training:
+                plan.scratch[self, 'dlin'] = plan.empty(plan.out_shape(self))
         xs = plan.out_shape(self.parent)
         cin = self.parent.shape['f']
         nb = plan.ctx.upconv_ws_bytes(self.n_f, cin, self.pool_shape, xs)
@@ -1381,16 +1388,25 @@ class UpConv(Conv):
             plan.join_side()                  # (the repack may run on the side stream)
 
         pre = plan.scratch.get((self, 'pre'), plan.out[self])
+        bn = self._bn()
+        dst = plan.scratch[self, 'lin'] if bn else pre
+        bias, act = (None, 'lin') if bn else (plan.param(self.b), self._lin_act())
 
         def run():
             if wp is not None:
-                plan.ctx.upconv3d_fwd_packed(plan.out[self.parent], wp, plan.param(self.b),
-                                             self.n_f, self.pool_shape, self._lin_act(), pre)
+                plan.ctx.upconv3d_fwd_packed(plan.out[self.parent], wp, bias,
+                                             self.n_f, self.pool_shape, act, dst)
             else:
                 plan.ctx.upconv3d_fwd(plan.out[self.parent], plan.param(self.w),
-                                      plan.param(self.b), self.pool_shape,
-                                      self._lin_act(), pre, plan.scratch[self, 'ws'])
+                                      bias, self.pool_shape,
+                                      act, dst, plan.scratch[self, 'ws'])
         plan.tuned('igemm', sig, cands, run)
+        if bn:
+            train = self.batch_normalisation == 'train'
+            plan.ctx.batchnorm_act_fwd(dst, plan.param(self.gamma), plan.param(self.b),
+                                       plan.param(self.mean), plan.param(self.std), train,
+                                       train and plan.step in ('SGD', 'Adam'), self._lin_act(),
+                                       pre, plan.scratch[self, 'bn_save'])
         if not self._plain_act():
             plan.ctx.act_fwd(pre, None, self.activation_func, plan.out[self])
 
@@ -1412,17 +1428,27 @@ class UpConv(Conv):
             # once, in place on the output gradient and outside the tuner's repeated `run`
             ctx.act_bwd(plan.grad[self], plan.scratch[self, 'pre'], None, self.activation_func,
                         plan.grad[self], None)
+        dout, act, dbias = plan.grad[self], self._lin_act(), plan.pgrad(self.b)
+        if self._bn():
+            # once, outside `run` (it ADDS to dgamma / dbias); the GEMMs then see the gradient
+            # of the bare upconvolution: no activation, no bias gradient of their own
+            ctx.batchnorm_act_bwd(dout, plan.scratch[self, 'lin'], plan.param(self.gamma),
+                                  plan.param(self.b), plan.scratch[self, 'bn_save'],
+                                  self.batch_normalisation == 'train', act,
+                                  plan.scratch[self, 'dlin'],
+                                  plan.pgrad(self.gamma) if self.gamma.apply_train else None, dbias)
+            dout, act, dbias = plan.scratch[self, 'dlin'], 'lin', None
 
         def run():
             if packed:
                 ctx.upconv3d_bwd_packed(plan.out[self.parent], wp_d, plan.out[self],
-                                        plan.grad[self], self.pool_shape, self._lin_act(),
-                                        dx, plan.pgrad(self.w), plan.pgrad(self.b),
+                                        dout, self.pool_shape, act,
+                                        dx, plan.pgrad(self.w), dbias,
                                         plan.scratch[self, 'ws'], accumulate=plan._capturing)
             else:
                 ctx.upconv3d_bwd(plan.out[self.parent], plan.param(self.w), plan.out[self],
-                                 plan.grad[self], self.pool_shape, self._lin_act(), dx,
-                                 plan.pgrad(self.w), plan.pgrad(self.b), plan.scratch[self, 'ws'])
+                                 dout, self.pool_shape, act, dx,
+                                 plan.pgrad(self.w), dbias, plan.scratch[self, 'ws'])
         plan.tuned('igemm', sigs['dgrad'][0], sigs['dgrad'][1] if dx is not None else [],
                    lambda: plan.tuned('wgrad', sigs['wgrad'][0], sigs['wgrad'][1], run))
         if dx is not None and not first:

@@ -2,10 +2,10 @@
 HIP path: 2-D convs (unit z axis) with train-mode batch normalisation, Perceptrons, softmax /
 NLL on 'b,f' tensors -- loss, probabilities, every parameter gradient (through the batch
 statistics), Adam steps with gamma's 3x weight decay and the running-statistics updates,
-against oracle/mnist_oracle.py (torch float64 autograd of the restated forward pass)."""
+against oracle/mnist_oracle.py (torch float64 autograd of the restated forward pass).  The ops of
+csrc/dense_bn.hip on their own: tests/test_batchnorm_gpu.py."""
 import numpy as np
 import pytest
-import torch
 
 from oracle import e2_oracle as O
 from oracle import mnist_oracle as MO
@@ -29,66 +29,6 @@ def all_params(m):
             if k in ('w', 'b', 'gamma', 'mean', 'std'):
                 out['%s_%s' % (node.name, k)] = p.get_value()
     return out
-
-
-def dev(a):
-    return torch.tensor(np.ascontiguousarray(a, np.float32), device="cuda")
-
-
-def test_dense_and_batchnorm_ops(ctx):
-    rng = np.random.RandomState(5)
-    x = rng.randn(20, 57).astype(np.float32)
-    w = rng.randn(57, 33).astype(np.float32)
-    dy = rng.randn(20, 33).astype(np.float32)
-    y = torch.empty(20, 33, device="cuda")
-    ctx.dense_fwd(dev(x), dev(w), y)
-    assert rel(y.cpu().numpy(), x.astype(np.float64) @ w) < 2e-6
-    dx = torch.full((20, 57), float("nan"), device="cuda")
-    ctx.dense_dgrad(dev(dy), dev(w), dx)
-    assert rel(dx.cpu().numpy(), dy.astype(np.float64) @ w.T) < 2e-6
-    ctx.dense_dgrad(dev(dy), dev(w), dx, accumulate=True)
-    assert rel(dx.cpu().numpy(), 2 * (dy.astype(np.float64) @ w.T)) < 2e-6
-    dw = torch.zeros(57, 33, device="cuda")
-    ctx.dense_wgrad(dev(x), dev(dy), dw, accumulate=True)
-    ctx.dense_wgrad(dev(x), dev(dy), dw, accumulate=True)
-    assert rel(dw.cpu().numpy(), 2 * (x.astype(np.float64).T @ dy)) < 2e-6
-    # batch norm + relu, train mode, gradient through the statistics, strided dx view
-    for shape in [(20, 12, 1, 12, 12), (3, 5, 2, 4, 7), (20, 200, 1, 1, 1)]:
-        xb = rng.randn(*shape).astype(np.float32) * 2 + 0.5
-        g = (rng.rand(shape[1]) + 0.5).astype(np.float32)
-        b = rng.randn(shape[1]).astype(np.float32) * 0.3
-        do = rng.randn(*shape).astype(np.float32)
-        X = torch.tensor(xb, dtype=torch.float64, requires_grad=True)
-        G = torch.tensor(g, dtype=torch.float64, requires_grad=True)
-        B = torch.tensor(b, dtype=torch.float64, requires_grad=True)
-        yb, mean, std = MO.batchnorm(X, G, B)
-        out_ref = MO.relu(yb)
-        (out_ref * torch.tensor(do, dtype=torch.float64)).sum().backward()
-        rm = torch.zeros(shape[1], device="cuda"); rs = torch.ones(shape[1], device="cuda")
-        out = torch.full(shape, float("nan"), device="cuda")
-        save = torch.zeros(2 * shape[1], device="cuda")
-        ctx.batchnorm_act_fwd(dev(xb), dev(g), dev(b), rm, rs, True, True, 'relu', out, save)
-        assert rel(out.cpu().numpy(), out_ref.detach().numpy()) < 1e-5
-        assert rel(save[:shape[1]].cpu().numpy(), mean.detach().numpy()) < 1e-5
-        assert rel(save[shape[1]:].cpu().numpy(), std.detach().numpy()) < 1e-5
-        assert rel(rm.cpu().numpy(), 0.0005 * mean.detach().numpy()) < 1e-5
-        assert rel(rs.cpu().numpy(), 0.9995 + 0.0005 * std.detach().numpy()) < 1e-6
-        big = torch.zeros((shape[0], shape[1], shape[2] + 2, shape[3] + 2, shape[4] + 3), device="cuda")
-        dxv = big[:, :, 1:-1, 1:-1, 2:-1]
-        dg = torch.zeros(shape[1], device="cuda"); db = torch.zeros(shape[1], device="cuda")
-        ctx.batchnorm_act_bwd(dev(do), dev(xb), dev(g), dev(b), save, True, 'relu', dxv, dg, db)
-        assert rel(dxv.cpu().numpy(), X.grad.numpy()) < 2e-5
-        assert rel(dg.cpu().numpy(), G.grad.numpy()) < 2e-5
-        assert rel(db.cpu().numpy(), B.grad.numpy()) < 2e-5
-        border = big.clone()
-        border[:, :, 1:-1, 1:-1, 2:-1] = 0
-        assert not border.any()                    # nothing written outside the view
-        # predict mode: stored statistics, constants of the gradient
-        rm2 = dev(rng.randn(shape[1])); rs2 = dev(rng.rand(shape[1]) + 0.5)
-        ctx.batchnorm_act_fwd(dev(xb), dev(g), dev(b), rm2, rs2, False, False, 'lin', out, save)
-        ref = (g / rs2.cpu().numpy()).reshape(1, -1, 1, 1, 1) * xb + \
-            (b - g * rm2.cpu().numpy() / rs2.cpu().numpy()).reshape(1, -1, 1, 1, 1)
-        assert rel(out.cpu().numpy(), ref) < 1e-5
 
 
 def test_mnist_config_parity():
