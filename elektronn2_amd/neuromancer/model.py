@@ -23,6 +23,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import graphutils, optimiser
+from .variables import reg_multiplier
 from .. import config
 
 logger = logging.getLogger('elektronn2log')
@@ -218,8 +219,7 @@ class Model(GraphManager):
             p._owner = self           # (set_value tells the model that its parameters changed)
             if p.apply_train:
                 seg_off.append(o)
-                r = p.apply_reg
-                seg_reg.append(float(r) if (r and r is not True) else (1.0 if r else 0.0))
+                seg_reg.append(reg_multiplier(p))
         seg_off.append(self.n_train)
         self.seg_off = torch.tensor(seg_off, dtype=torch.int64, device=ctx.device)
         self.seg_reg = torch.tensor(seg_reg or [0.0], dtype=torch.float32, device=ctx.device)

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from .. import backend
+from .variables import reg_multiplier
 
 _ctx = None
 
@@ -611,13 +612,10 @@ class Plan(object):
                 up.append((w5, wp, mode))
         if not order:
             return
-
-        def mult(p):
-            r = p.apply_reg
-            return float(r) if (r and r is not True) else (1.0 if r else 0.0)
-        ujobs = [(m._slots[k][0], by_param[k][2], by_param[k][3], by_param[k][1], mult(by_param[k][0]))
+        ujobs = [(m._slots[k][0], by_param[k][2], by_param[k][3], by_param[k][1],
+                  reg_multiplier(by_param[k][0]))
                  for k in order]
-        rests = [(m._slots[id(p)][0], m._slots[id(p)][1], mult(p)) for p in m._param_list
+        rests = [(m._slots[id(p)][0], m._slots[id(p)][1], reg_multiplier(p)) for p in m._param_list
                  if p.apply_train and id(p) not in by_param]
         self._upd = self.ctx.make_upd_jobs(ujobs, rests)
         self._pack_dev_up = self.ctx.make_pack_jobs(up) if up else None

@@ -14,7 +14,17 @@ import numpy as np
 
 from .graphutils import floatX, as_floatX
 
-__all__ = ['VariableParam', 'VariableWeight', 'ConstantParam', 'initweights']
+__all__ = ['VariableParam', 'VariableWeight', 'ConstantParam', 'initweights', 'reg_multiplier']
+
+
+def reg_multiplier(p):
+    """Weight-decay multiplier of parameter ``p`` in the optimisers' segment tables
+    (optimiser.py:148-155, :246-248, :311-313): 0 without ``apply_reg``, ``apply_reg`` itself
+    only where it is > 1, and 1 otherwise -- a fractional ``apply_reg`` decays like ``True``."""
+    r = p.apply_reg
+    if not r:
+        return 0.0
+    return float(r) if r > 1 else 1.0
 
 
 class VariableParam(object):
