@@ -287,6 +287,7 @@ static int conv1_fwd(e2_ctx* ctx, const e2_tensor5* x, const float* w, const flo
                      int kh, int kw, int py, int px, int act, const e2_tensor5* out, void* next_xb,
                      int next_kg) {
   E2_REQUIRE(ctx && w && bias, "conv1_pool_act_fwd: null argument");
+  E2_REQUIRE(act == E2_ACT_LIN || act == E2_ACT_RELU, "conv1_pool_act_fwd: bad act %d", act);
   const int v = first_supported(1, kh, kw, 1, py, px);
   E2_REQUIRE(v, "conv1_pool_act_fwd: unsupported kernel/pool %dx%d / %dx%d", kh, kw, py, px);
   First p{};
@@ -322,6 +323,7 @@ extern "C" int e2_conv1_pool_act_bwd(e2_ctx* ctx, const e2_tensor5* x, const flo
                                      int py, int px, int act, float* dw, float* dbias,
                                      void* ws, size_t ws_bytes) {
   E2_REQUIRE(ctx && w && bias && dw && dbias && ws, "conv1_pool_act_bwd: null argument");
+  E2_REQUIRE(act == E2_ACT_LIN || act == E2_ACT_RELU, "conv1_pool_act_bwd: bad act %d", act);
   const int v = first_supported(1, kh, kw, 1, py, px);
   E2_REQUIRE(v, "conv1_pool_act_bwd: unsupported kernel/pool %dx%d / %dx%d", kh, kw, py, px);
   First p{};

@@ -229,10 +229,11 @@ int e2_conv3d_pack_multi_ex(e2_ctx*, const void* jobs_dev, int njobs, int max_ta
 
 /* ---- first layer, fused (Conv node on a 1-channel input: conv -> pool -> +b ->
  *      act in one pass; neural.py:662-712).  Supported: kd = 1, pool z = 1 and
- *      (kh,kw,py,px) in {(4,4,2,2), (6,6,2,2)} -- the neuro3d nets' first layers;
- *      e2_conv1_supported() tells.  The backward RECOMPUTES the conv values
- *      instead of reading a stored conv output; dw / dbias are accumulated
- *      (zero them first). ---------------------------------------------------- */
+ *      (kh,kw,py,px) in {(4,4,2,2), (6,6,2,2)} -- the neuro3d nets' first layers --
+ *      or (3,3,1,1), the U-Net stem; e2_conv1_supported() tells.  act: E2_ACT_LIN
+ *      or E2_ACT_RELU, any other value is an error.  The backward RECOMPUTES the
+ *      conv values instead of reading a stored conv output; dw / dbias are
+ *      accumulated (zero them first). ---------------------------------------- */
 int e2_conv1_supported(int cin, int kd, int kh, int kw, int pz, int py, int px);
 int e2_conv1_pool_act_fwd(e2_ctx*, const e2_tensor5* x, const float* w,
                           const float* bias, int cout, int kh, int kw, int py,

@@ -758,7 +758,8 @@ def test_several_steps_per_launch_in_bf16_mode(process_bf16):
 
 
 @pytest.mark.parametrize("k,pool,cout,sp", [((1, 4, 4), (1, 2, 2), 20, (3, 35, 73)), ((1, 6, 6), (1, 2, 2), 20, (2, 37, 41)),
-                                            ((1, 3, 3), (1, 1, 1), 32, (2, 20, 70)), ((1, 4, 4), (1, 2, 2), 7, (1, 19, 23))])
+                                            ((1, 3, 3), (1, 1, 1), 32, (2, 20, 70)), ((1, 4, 4), (1, 2, 2), 7, (1, 19, 23)),
+                                            ((1, 6, 6), (1, 2, 2), 29, (2, 37, 41)), ((1, 3, 3), (1, 1, 1), 21, (2, 20, 70))])
 def test_first_layer_writes_the_next_layers_input_image(ctx, k, pool, cout, sp):
     """e2_conv1_pool_act_fwd_bf16: the fused first layer (conv + pool + bias + relu on the matrix
     cores) with the next conv's channels-last bf16 image as a second output: the f32 output is
