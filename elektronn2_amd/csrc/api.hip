@@ -55,7 +55,7 @@ extern "C" int e2_ctx_create(int device, e2_ctx** out) {
   c->image_rows = 0;
   c->last_fill_ptr = nullptr;
   c->last_fill_n = 0;
-  c->tiling[0][0] = c->tiling[1][0] = 0;
+  c->tiling[0][0] = c->tiling[1][0] = 0;       // (tiling_v: empty by its initialisers)
   c->last_launch[0] = 0;
   c->tiling_fallbacks = 0;
   for (int i = 0; i < 32; ++i) c->fork_ev[i] = nullptr;
@@ -129,20 +129,19 @@ static int image_dims(const e2_ctx* ctx, int cout, int cin, int* ciP, int* coP) 
   return 0;
 }
 
+/* The one place that reads a tiling string (grammar and forms: e2hip.h; e2_parse_tiling,
+ * conv_host.hpp): the launches read ctx->tiling_v, the string stays for messages and the debug log. */
 extern "C" int e2_set_tiling(e2_ctx* ctx, int kind, const char* cfg) {
   E2_REQUIRE(ctx, "e2_set_tiling: null context");
   E2_REQUIRE(kind == E2_TILING_IGEMM || kind == E2_TILING_WGRAD, "e2_set_tiling: unknown kind %d", kind);
   if (!cfg) cfg = "";
-  E2_REQUIRE(strlen(cfg) < sizeof(ctx->tiling[0]), "e2_set_tiling: configuration string too long");
-  if (cfg[0]) {
-    int v[5], n = sscanf(cfg, "%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4]);
-    int v5 = 0, v6 = 0, v7 = 0;
-    if (n == 5 && kind == E2_TILING_IGEMM) n += sscanf(cfg, "%*d,%*d,%*d,%*d,%*d,%d,%d,%d", &v5, &v6, &v7);
-    E2_REQUIRE(kind == E2_TILING_IGEMM ? (n == 4 || (n == 3 && (v[0] == 32 || v[0] == 1)) || (n == 8 && v[0] == 4)) : n == 5,
-               "e2_set_tiling: '%s' is not %s", cfg,
-               kind == E2_TILING_IGEMM ? "\"MT,NT,CC,SK\", \"4,MG,NT,CC,SK,WM,WN,G\", \"1,MT,NT\" or \"32,MB,NB\"" : "\"MT,NT,WK,BP,PS\"");
-  }
+  E2_REQUIRE(strlen(cfg) < (size_t)kE2TilingChars, "e2_set_tiling: configuration string too long");
+  E2Tiling t;
+  E2_REQUIRE(e2_parse_tiling(cfg, &t) && e2_tiling_accepted(kind, t), "e2_set_tiling: '%s' is not %s", cfg,
+             kind == E2_TILING_IGEMM ? "\"MT,NT,CC,SK\", \"4,MG,NT,CC,SK,WM,WN,G\", \"1,MT,NT\", \"1,MT,NT,KC,0\" or \"32,MB,NB\""
+                                     : "\"MT,NT,WK,BP,PS\"");
   strcpy(ctx->tiling[kind], cfg);
+  ctx->tiling_v[kind] = t;
   return 0;
 }
 
@@ -254,26 +253,39 @@ extern "C" int e2_conv3d_pack(e2_ctx* ctx, const float* w, int cout, int cin, in
                           ciP, coP, 1, 1);
 }
 
+// the shape rule of the packed launches: `out` has `rows` channels and the extents in - k + 1
+static int conv_shape_ok(const char* who, const char* out_name, const e2_tensor5* out,
+                         const char* in_name, const e2_tensor5* in, int rows, int kd, int kh, int kw) {
+  const int d = in->d - kd + 1, h = in->h - kh + 1, w = in->w - kw + 1;
+  E2_REQUIRE(out->n == in->n && out->c == rows && out->d == d && out->h == h && out->w == w,
+             "%s: %s is (%d,%d,%d,%d,%d) but %s (%d,%d,%d,%d,%d) with kernel %d,%d,%d gives "
+             "(%d,%d,%d,%d,%d)", who, out_name, out->n, out->c, out->d, out->h, out->w, in_name,
+             in->n, in->c, in->d, in->h, in->w, kd, kh, kw, in->n, rows, d, h, w);
+  return 0;
+}
+
+// checks and arguments that the forward (x -> y) and the data gradient (padded dy -> dx) share:
+// both views, the shape rule, the GEMM's arguments and the dims of the image it reads
+static int conv_packed_args(e2_ctx* ctx, const char* who, const char* in_name, const e2_tensor5* in,
+                            const void* wp, int rows, int kd, int kh, int kw, const char* out_name,
+                            const e2_tensor5* out, IgemmArgs* a) {
+  E2_REQUIRE(ctx && wp, "%s: null argument", who);
+  char nm[96];
+  snprintf(nm, sizeof(nm), "%s %s", who, in_name);
+  if (int rc = view_ok(in, nm)) return rc;
+  snprintf(nm, sizeof(nm), "%s %s", who, out_name);
+  if (int rc = view_ok(out, nm)) return rc;
+  if (int rc = conv_shape_ok(who, out_name, out, in_name, in, rows, kd, kh, kw)) return rc;
+  *a = igemm_args(*in, *out, (const float*)wp, rows, kd, kh, kw);
+  return image_dims(ctx, rows, in->c, &a->ciP, &a->coP);
+}
+
 static int conv_fwd_packed(e2_ctx* ctx, const e2_tensor5* x, const void* wp, int cout, int kd,
                            int kh, int kw, const e2_tensor5* y, int64_t part_stride,
                            int max_parts, int* nparts) {
-  E2_REQUIRE(ctx && wp, "conv3d_fwd: null argument");
-  if (int rc = view_ok(x, "conv3d_fwd x")) return rc;
-  if (int rc = view_ok(y, "conv3d_fwd y")) return rc;
   E2_REQUIRE(kd >= 1 && kh >= 1 && kw >= 1, "conv3d_fwd: bad kernel %d,%d,%d", kd, kh, kw);
-  E2_REQUIRE(y->n == x->n && y->c == cout && y->d == x->d - kd + 1 &&
-                 y->h == x->h - kh + 1 && y->w == x->w - kw + 1,
-             "conv3d_fwd: y is (%d,%d,%d,%d,%d), expected (%d,%d,%d,%d,%d)", y->n, y->c,
-             y->d, y->h, y->w, x->n, cout, x->d - kd + 1, x->h - kh + 1, x->w - kw + 1);
   IgemmArgs a;
-  a.in = x->ptr; a.wp = (const float*)wp; a.out = y->ptr;
-  a.N = x->n; a.Cin = x->c; a.Cout = cout;
-  a.kd = kd; a.kh = kh; a.kw = kw;
-  a.Do = y->d; a.Ho = y->h; a.Wo = y->w;
-  a.isN = x->sn; a.isC = x->sc; a.isZ = x->sd; a.isY = x->sh;
-  a.osN = y->sn; a.osC = y->sc; a.osZ = y->sd; a.osY = y->sh;
-  if (int rc = image_dims(ctx, cout, x->c, &a.ciP, &a.coP)) return rc;
-  a.upz = a.upy = a.upx = 1;
+  if (int rc = conv_packed_args(ctx, "conv3d_fwd", "x", x, wp, cout, kd, kh, kw, "y", y, &a)) return rc;
   a.parts_max = max_parts; a.part_stride = part_stride; a.nparts = nparts;
   return e2i_igemm_conv(ctx, a);
 }
@@ -292,27 +304,13 @@ extern "C" int e2_conv3d_fwd_packed_parts(e2_ctx* ctx, const e2_tensor5* x, cons
 extern "C" int e2_conv3d_fwd_packed_act(e2_ctx* ctx, const e2_tensor5* x, const void* wp,
                                         int cout, int kd, int kh, int kw, const float* bias,
                                         int act, const e2_tensor5* out) {
-  E2_REQUIRE(ctx && wp && bias, "conv3d_fwd_act: null argument");
+  E2_REQUIRE(bias, "conv3d_fwd_act: null argument");
   E2_REQUIRE(act == E2_ACT_LIN || act == E2_ACT_RELU, "conv3d_fwd_act: bad act %d", act);
-  if (int rc = view_ok(x, "conv3d_fwd_act x")) return rc;
-  if (int rc = view_ok(out, "conv3d_fwd_act out")) return rc;
   E2_REQUIRE(kd >= 1 && kh >= 1 && kw >= 1, "conv3d_fwd_act: bad kernel %d,%d,%d", kd, kh, kw);
-  E2_REQUIRE(out->n == x->n && out->c == cout && out->d == x->d - kd + 1 &&
-                 out->h == x->h - kh + 1 && out->w == x->w - kw + 1,
-             "conv3d_fwd_act: out is (%d,%d,%d,%d,%d), expected (%d,%d,%d,%d,%d)", out->n,
-             out->c, out->d, out->h, out->w, x->n, cout, x->d - kd + 1, x->h - kh + 1,
-             x->w - kw + 1);
+  IgemmArgs a;
+  if (int rc = conv_packed_args(ctx, "conv3d_fwd_act", "x", x, wp, cout, kd, kh, kw, "out", out, &a)) return rc;
   E2_REQUIRE(out->sh == out->w && (kw == 1 || kw == 3 || kw == 4 || kw == 5),
              "conv3d_fwd_act: needs dense output rows and a kernel width of 1, 3, 4 or 5");
-  IgemmArgs a;
-  a.in = x->ptr; a.wp = (const float*)wp; a.out = out->ptr;
-  a.N = x->n; a.Cin = x->c; a.Cout = cout;
-  a.kd = kd; a.kh = kh; a.kw = kw;
-  a.Do = out->d; a.Ho = out->h; a.Wo = out->w;
-  a.isN = x->sn; a.isC = x->sc; a.isZ = x->sd; a.isY = x->sh;
-  a.osN = out->sn; a.osC = out->sc; a.osZ = out->sd; a.osY = out->sh;
-  if (int rc = image_dims(ctx, cout, x->c, &a.ciP, &a.coP)) return rc;
-  a.upz = a.upy = a.upx = 1;
   a.bias = bias; a.act = act;
   return e2i_igemm_conv(ctx, a);
 }
@@ -320,25 +318,8 @@ extern "C" int e2_conv3d_fwd_packed_act(e2_ctx* ctx, const e2_tensor5* x, const 
 static int conv_dgrad_packed(e2_ctx* ctx, const e2_tensor5* dy_pad, const void* wp, int cin,
                              int kd, int kh, int kw, const e2_tensor5* dx, int64_t part_stride,
                              int max_parts, int* nparts) {
-  E2_REQUIRE(ctx && wp, "conv3d_dgrad: null argument");
-  if (int rc = view_ok(dy_pad, "conv3d_dgrad dy_pad")) return rc;
-  if (int rc = view_ok(dx, "conv3d_dgrad dx")) return rc;
-  E2_REQUIRE(dx->n == dy_pad->n && dx->c == cin && dx->d == dy_pad->d - kd + 1 &&
-                 dx->h == dy_pad->h - kh + 1 && dx->w == dy_pad->w - kw + 1,
-             "conv3d_dgrad: dx is (%d,%d,%d,%d,%d) but padded dy (%d,%d,%d,%d,%d) with "
-             "kernel %d,%d,%d gives (%d,%d,%d,%d,%d)",
-             dx->n, dx->c, dx->d, dx->h, dx->w, dy_pad->n, dy_pad->c, dy_pad->d, dy_pad->h,
-             dy_pad->w, kd, kh, kw, dy_pad->n, cin, dy_pad->d - kd + 1, dy_pad->h - kh + 1,
-             dy_pad->w - kw + 1);
   IgemmArgs a;
-  a.in = dy_pad->ptr; a.wp = (const float*)wp; a.out = dx->ptr;
-  a.N = dx->n; a.Cin = dy_pad->c; a.Cout = cin;
-  a.kd = kd; a.kh = kh; a.kw = kw;
-  a.Do = dx->d; a.Ho = dx->h; a.Wo = dx->w;
-  a.isN = dy_pad->sn; a.isC = dy_pad->sc; a.isZ = dy_pad->sd; a.isY = dy_pad->sh;
-  a.osN = dx->sn; a.osC = dx->sc; a.osZ = dx->sd; a.osY = dx->sh;
-  if (int rc = image_dims(ctx, cin, dy_pad->c, &a.ciP, &a.coP)) return rc;
-  a.upz = a.upy = a.upx = 1;
+  if (int rc = conv_packed_args(ctx, "conv3d_dgrad", "dy_pad", dy_pad, wp, cin, kd, kh, kw, "dx", dx, &a)) return rc;
   E2_REQUIRE(ctx->dgrad_zinset <= kd - 1, "conv3d_dgrad: z inset %d of a border of %d planes",
              ctx->dgrad_zinset, kd - 1);
   a.zpad = kd - 1 - ctx->dgrad_zinset;
@@ -365,35 +346,22 @@ extern "C" int e2_conv3d_dgrad_packed_actbwd(e2_ctx* ctx, const e2_tensor5* dy_p
                                              const float* bias_prev,
                                              const e2_tensor5* dy_pad_prev, int pd, int ph,
                                              int pw, float* dbias_prev) {
-  E2_REQUIRE(ctx && wp, "conv3d_dgrad_actbwd: null argument");
-  E2_REQUIRE(act_prev == E2_ACT_LIN || act_prev == E2_ACT_RELU, "conv3d_dgrad_actbwd: bad act %d", act_prev);
+  const char* who = "conv3d_dgrad_actbwd";
+  E2_REQUIRE(ctx && wp, "%s: null argument", who);
+  E2_REQUIRE(act_prev == E2_ACT_LIN || act_prev == E2_ACT_RELU, "%s: bad act %d", who, act_prev);
   if (int rc = view_ok(dy_pad, "conv3d_dgrad_actbwd dy_pad")) return rc;
   if (int rc = view_ok(out_prev, "conv3d_dgrad_actbwd out_prev")) return rc;
   if (int rc = view_ok(dy_pad_prev, "conv3d_dgrad_actbwd dy_pad_prev")) return rc;
-  E2_REQUIRE(pd >= 0 && ph >= 0 && pw >= 0, "conv3d_dgrad_actbwd: negative padding");
+  E2_REQUIRE(pd >= 0 && ph >= 0 && pw >= 0, "%s: negative padding", who);
   const e2_tensor5* o = out_prev; const e2_tensor5* q = dy_pad_prev;
-  E2_REQUIRE(o->n == dy_pad->n && o->c == cin && o->d == dy_pad->d - kd + 1 &&
-                 o->h == dy_pad->h - kh + 1 && o->w == dy_pad->w - kw + 1,
-             "conv3d_dgrad_actbwd: out_prev is (%d,%d,%d,%d,%d) but padded dy (%d,%d,%d,%d,%d) "
-             "with kernel %d,%d,%d gives (%d,%d,%d,%d,%d)", o->n, o->c, o->d, o->h, o->w,
-             dy_pad->n, dy_pad->c, dy_pad->d, dy_pad->h, dy_pad->w, kd, kh, kw, dy_pad->n, cin,
-             dy_pad->d - kd + 1, dy_pad->h - kh + 1, dy_pad->w - kw + 1);
+  if (int rc = conv_shape_ok(who, "out_prev", o, "dy_pad", dy_pad, cin, kd, kh, kw)) return rc;
   E2_REQUIRE(q->n == o->n && q->c == o->c && q->d == o->d + 2 * pd && q->h == o->h + 2 * ph &&
                  q->w == o->w + 2 * pw,
-             "conv3d_dgrad_actbwd: dy_pad_prev is (%d,%d,%d,%d,%d), expected (%d,%d,%d,%d,%d)",
+             "%s: dy_pad_prev is (%d,%d,%d,%d,%d), expected (%d,%d,%d,%d,%d)", who,
              q->n, q->c, q->d, q->h, q->w, o->n, o->c, o->d + 2 * pd, o->h + 2 * ph, o->w + 2 * pw);
-  e2_tensor5 dx = *q;                           // the interior view
-  dx.ptr = q->ptr + (int64_t)pd * q->sd + (int64_t)ph * q->sh + pw;
-  dx.d = o->d; dx.h = o->h; dx.w = o->w;
-  IgemmArgs a;
-  a.in = dy_pad->ptr; a.wp = (const float*)wp; a.out = dx.ptr;
-  a.N = dx.n; a.Cin = dy_pad->c; a.Cout = cin;
-  a.kd = kd; a.kh = kh; a.kw = kw;
-  a.Do = dx.d; a.Ho = dx.h; a.Wo = dx.w;
-  a.isN = dy_pad->sn; a.isC = dy_pad->sc; a.isZ = dy_pad->sd; a.isY = dy_pad->sh;
-  a.osN = dx.sn; a.osC = dx.sc; a.osZ = dx.sd; a.osY = dx.sh;
+  e2_tensor5 dx = e2_interior(*q, pd, ph, pw);
+  IgemmArgs a = igemm_args(*dy_pad, dx, (const float*)wp, cin, kd, kh, kw);
   if (int rc = image_dims(ctx, cin, dy_pad->c, &a.ciP, &a.coP)) return rc;
-  a.upz = a.upy = a.upx = 1;
   // (e2_set_dgrad_zinset is NOT read here: this launch writes the parent's PADDED gradient and is
   // only issued for a valid conv behind a valid conv -- Conv._actbwd_into_parent)
   a.zpad = kd - 1;
@@ -432,8 +400,23 @@ extern "C" int e2_conv3d_dgrad(e2_ctx* ctx, const e2_tensor5* dy_pad, const floa
   return e2_conv3d_dgrad_packed(ctx, dy_pad, ws, cin, kd, kh, kw, dx);
 }
 
+// the shape rule of the weight gradients: dy (unpadded extents) is x - k + 1
+static int wgrad_shape_ok(const char* who, const e2_tensor5* x, const e2_tensor5& dy, int kd, int kh, int kw) {
+  E2_REQUIRE(dy.n == x->n && dy.d == x->d - kd + 1 && dy.h == x->h - kh + 1 && dy.w == x->w - kw + 1 &&
+                 dy.d > 0 && dy.h > 0 && dy.w > 0,
+             "%s: dy spatial (%d,%d,%d) != x (%d,%d,%d) - k + 1, kernel %d,%d,%d", who, dy.d, dy.h, dy.w,
+             x->d, x->h, x->w, kd, kh, kw);
+  return 0;
+}
+
 static int wgrad_impl(e2_ctx* ctx, const e2_tensor5* x, const e2_tensor5* dy, float* dw,
-                      int kd, int kh, int kw, int accumulate);
+                      int kd, int kh, int kw, int accumulate) {
+  E2_REQUIRE(ctx && dw, "conv3d_wgrad: null argument");
+  if (int rc = view_ok(x, "conv3d_wgrad x")) return rc;
+  if (int rc = view_ok(dy, "conv3d_wgrad dy")) return rc;
+  if (int rc = wgrad_shape_ok("conv3d_wgrad", x, *dy, kd, kh, kw)) return rc;
+  return e2i_wgrad_conv(ctx, wgrad_args(*x, *dy, dw, kd, kh, kw, accumulate, 0));
+}
 extern "C" int e2_conv3d_wgrad(e2_ctx* ctx, const e2_tensor5* x, const e2_tensor5* dy,
                                float* dw, int kd, int kh, int kw) {
   return wgrad_impl(ctx, x, dy, dw, kd, kh, kw, 0);
@@ -442,28 +425,6 @@ extern "C" int e2_conv3d_wgrad_acc(e2_ctx* ctx, const e2_tensor5* x, const e2_te
                                    float* dw, int kd, int kh, int kw) {
   return wgrad_impl(ctx, x, dy, dw, kd, kh, kw, 1);
 }
-static int wgrad_impl(e2_ctx* ctx, const e2_tensor5* x, const e2_tensor5* dy, float* dw,
-                      int kd, int kh, int kw, int accumulate) {
-  E2_REQUIRE(ctx && dw, "conv3d_wgrad: null argument");
-  if (int rc = view_ok(x, "conv3d_wgrad x")) return rc;
-  if (int rc = view_ok(dy, "conv3d_wgrad dy")) return rc;
-  E2_REQUIRE(dy->n == x->n && dy->d == x->d - kd + 1 && dy->h == x->h - kh + 1 &&
-                 dy->w == x->w - kw + 1,
-             "conv3d_wgrad: dy spatial (%d,%d,%d) != x (%d,%d,%d) - k + 1", dy->d, dy->h,
-             dy->w, x->d, x->h, x->w);
-  WgradArgs a;
-  a.x = x->ptr; a.dy = dy->ptr; a.dw = dw;
-  a.N = x->n; a.Cin = x->c; a.Cout = dy->c;
-  a.kd = kd; a.kh = kh; a.kw = kw;
-  a.Do = dy->d; a.Ho = dy->h; a.Wo = dy->w;
-  a.xsN = x->sn; a.xsC = x->sc; a.xsZ = x->sd; a.xsY = x->sh;
-  a.dsN = dy->sn; a.dsC = dy->sc; a.dsZ = dy->sd; a.dsY = dy->sh;
-  a.flip = 1;
-  a.upR = 1;
-  a.accumulate = accumulate;
-  a.dy_padded = 0;
-  return e2i_wgrad_conv(ctx, a);
-}
 
 extern "C" int e2_conv3d_wgrad_pad(e2_ctx* ctx, const e2_tensor5* x, const e2_tensor5* dy_pad,
                                    float* dw, int kd, int kh, int kw, int accumulate) {
@@ -471,26 +432,9 @@ extern "C" int e2_conv3d_wgrad_pad(e2_ctx* ctx, const e2_tensor5* x, const e2_te
   if (int rc = view_ok(x, "conv3d_wgrad_pad x")) return rc;
   if (int rc = view_ok(dy_pad, "conv3d_wgrad_pad dy_pad")) return rc;
   E2_REQUIRE(kd >= 1 && kh >= 1 && kw >= 1, "conv3d_wgrad_pad: bad kernel");
-  const int Do = dy_pad->d - 2 * (kd - 1), Ho = dy_pad->h - 2 * (kh - 1),
-            Wo = dy_pad->w - 2 * (kw - 1);
-  E2_REQUIRE(dy_pad->n == x->n && Do == x->d - kd + 1 && Ho == x->h - kh + 1 &&
-                 Wo == x->w - kw + 1 && Do > 0 && Ho > 0 && Wo > 0,
-             "conv3d_wgrad_pad: padded dy (%d,%d,%d) does not match x (%d,%d,%d), kernel %d,%d,%d",
-             dy_pad->d, dy_pad->h, dy_pad->w, x->d, x->h, x->w, kd, kh, kw);
-  WgradArgs a;
-  a.x = x->ptr;
-  a.dy = dy_pad->ptr + (int64_t)(kd - 1) * dy_pad->sd + (int64_t)(kh - 1) * dy_pad->sh + (kw - 1);
-  a.dw = dw;
-  a.N = x->n; a.Cin = x->c; a.Cout = dy_pad->c;
-  a.kd = kd; a.kh = kh; a.kw = kw;
-  a.Do = Do; a.Ho = Ho; a.Wo = Wo;
-  a.xsN = x->sn; a.xsC = x->sc; a.xsZ = x->sd; a.xsY = x->sh;
-  a.dsN = dy_pad->sn; a.dsC = dy_pad->sc; a.dsZ = dy_pad->sd; a.dsY = dy_pad->sh;
-  a.flip = 1;
-  a.upR = 1;
-  a.accumulate = accumulate;
-  a.dy_padded = 1;
-  return e2i_wgrad_conv(ctx, a);
+  const e2_tensor5 dy = e2_interior(*dy_pad, kd - 1, kh - 1, kw - 1);
+  if (int rc = wgrad_shape_ok("conv3d_wgrad_pad", x, dy, kd, kh, kw)) return rc;
+  return e2i_wgrad_conv(ctx, wgrad_args(*x, dy, dw, kd, kh, kw, accumulate, 1));
 }
 
 // ---------------------------------------------------------------------------
@@ -527,7 +471,10 @@ static int upconv_fwd(e2_ctx* ctx, const e2_tensor5* x, const float* w, const fl
                  y->w == x->w * px, "upconv3d_fwd: y shape mismatch");
   E2_REQUIRE(bias || act == E2_ACT_LIN, "upconv3d_fwd: act needs bias");
   const int R = pz * py * px;
-  IgemmArgs a;
+  // one GEMM row per (output channel, sub-position); the epilogue scatters depth-to-space into y
+  IgemmArgs a = igemm_args(*x, *y, wp, cout * R, 1, 1, 1);
+  a.Do = x->d; a.Ho = x->h; a.Wo = x->w;
+  a.upz = pz; a.upy = py; a.upx = px;
   e2i_pack_dims(cout * R, x->c, &a.ciP, &a.coP);
   if (!wp) {
     E2_REQUIRE(ws_bytes >= sizeof(float) * up_pack_floats(cout, x->c, R),
@@ -535,15 +482,8 @@ static int upconv_fwd(e2_ctx* ctx, const e2_tensor5* x, const float* w, const fl
     if (int rc = e2i_pack_weights(ctx, w, (float*)ws, cout * R, x->c, 1, 1, 1,
                                   (int64_t)x->c * R, R, 0, a.ciP, a.coP, R, 1))
       return rc;
-    wp = (const float*)ws;
+    a.wp = (const float*)ws;
   }
-  a.in = x->ptr; a.wp = wp; a.out = y->ptr;
-  a.N = x->n; a.Cin = x->c; a.Cout = cout * R;
-  a.kd = a.kh = a.kw = 1;
-  a.Do = x->d; a.Ho = x->h; a.Wo = x->w;
-  a.isN = x->sn; a.isC = x->sc; a.isZ = x->sd; a.isY = x->sh;
-  a.osN = y->sn; a.osC = y->sc; a.osZ = y->sd; a.osY = y->sh;
-  a.upz = pz; a.upy = py; a.upx = px;
   int fused = 0;                 // (the pointwise GEMM applies bias + act in its epilogue)
   a.up_bias = bias; a.up_act = act; a.up_bias_done = &fused;
   if (int rc = e2i_igemm_conv(ctx, a)) return rc;
@@ -596,41 +536,27 @@ static int upconv_bwd(e2_ctx* ctx, const e2_tensor5* x, const float* w,
   if (dbias && !accumulate)
     if (int rc = e2i_fill_flat(ctx, dbias, (size_t)cout, 0.f)) return rc;
   if (int rc = e2i_upconv_dpre_s2d(ctx, dout, y, pz, py, px, act, s2d, dbias)) return rc;
-  const long S = (long)x->d * x->h * x->w;
+  // the dense space-to-depth image of dpre: (n, cout * R, d, h, w) of the low resolution
+  const e2_tensor5 dpre = e2_dense_view(s2d, x->n, cout * R, x->d, x->h, x->w);
   if (dx) {
     if (int rc = view_ok(dx, "upconv3d_bwd dx")) return rc;
     E2_REQUIRE(dx->n == x->n && dx->c == cin && dx->d == x->d && dx->h == x->h &&
                    dx->w == x->w, "upconv3d_bwd: dx shape mismatch");
-    IgemmArgs a;
+    IgemmArgs a = igemm_args(dpre, *dx, wp_d ? wp_d : wp, cin, 1, 1, 1);
     e2i_pack_dims(cin, cout * R, &a.ciP, &a.coP);
     // Wp[ic' = co*R + r][oc = ci] = w[co][ci][r]
     if (!wp_d)
       if (int rc = e2i_pack_weights(ctx, w, wp, cin, cout * R, 1, 1, 1, R, (int64_t)cin * R,
                                     0, a.ciP, a.coP, 1, R))
         return rc;
-    a.in = s2d; a.wp = wp_d ? wp_d : wp; a.out = dx->ptr;
-    a.N = x->n; a.Cin = cout * R; a.Cout = cin;
-    a.kd = a.kh = a.kw = 1;
-    a.Do = x->d; a.Ho = x->h; a.Wo = x->w;
-    a.isN = (long)cout * R * S; a.isC = S; a.isZ = (long)x->h * x->w; a.isY = x->w;
-    a.osN = dx->sn; a.osC = dx->sc; a.osZ = dx->sd; a.osY = dx->sh;
-    a.upz = a.upy = a.upx = 1;
     if (int rc = e2i_igemm_conv(ctx, a)) return rc;
   }
   if (dw) {
-    WgradArgs g;
-    g.x = x->ptr; g.dy = s2d; g.dw = dw;
-    g.N = x->n; g.Cin = cin; g.Cout = cout * R;
-    g.kd = g.kh = g.kw = 1;
     // 1x1x1 taps: the dense space-to-depth image IS its own zero-padded form (no border,
     // no gap columns), and the workspace leaves 128 B behind it: the direct kernel applies
-    g.dy_padded = 1;
-    g.Do = x->d; g.Ho = x->h; g.Wo = x->w;
-    g.xsN = x->sn; g.xsC = x->sc; g.xsZ = x->sd; g.xsY = x->sh;
-    g.dsN = (long)cout * R * S; g.dsC = S; g.dsZ = (long)x->h * x->w; g.dsY = x->w;
+    WgradArgs g = wgrad_args(*x, dpre, dw, 1, 1, 1, accumulate, 1);
     g.flip = 0;
     g.upR = R;
-    g.accumulate = accumulate;
     if (int rc = e2i_wgrad_conv(ctx, g)) return rc;
   }
   return 0;

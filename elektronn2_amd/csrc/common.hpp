@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string>
 #include "../../include/e2hip.h"
+#include "conv_host.hpp"
 
 struct e2_ctx {
   int device;
@@ -19,7 +20,8 @@ struct e2_ctx {
   int skip_zero_fill;  // e2_set_skip_zero_fill: split-K outputs were zeroed by the caller
   float* last_fill_ptr;     // flat region the last conv launch zero-filled (n = 0: none)
   size_t last_fill_n;
-  char tiling[2][64];       // e2_set_tiling: forced tiling of the igemm / wgrad launches ("" = cost model)
+  char tiling[2][kE2TilingChars];   // e2_set_tiling: forced tiling of the igemm / wgrad launches ("" = cost model)
+  E2Tiling tiling_v[2];     // ... parsed there, once; the launches read this (the string: messages, debug log)
   int loss_sum_mode;        // e2_set_loss_grad_mode: 1 = NLL gradients are NOT divided by the labelled count
   float* loss_count_out;    // ... and the count is also written here (the slot behind the gradient arena)
   int input_slack;          // e2_set_input_slack: finite readable bytes behind the x of the launches that follow
@@ -29,9 +31,7 @@ struct e2_ctx {
   unsigned tiling_fallbacks;   // launches since e2_ctx_create whose forced tiling was NOT the one that ran
 };
 
-// what decided the tiling of a launch (third word of e2_last_launch)
-enum { E2_SRC_MODEL = 0, E2_SRC_FORCED = 1, E2_SRC_FALLBACK = 2 };
-// record the conv GEMM launch that is about to be issued (api.hip)
+// record the conv GEMM launch that is about to be issued (api.hip; src: E2_SRC_*, conv_host.hpp)
 void e2_note_launch(e2_ctx* ctx, const char* family, int src, const char* fmt, ...);
 
 // Debug switches (timing ablations, in-kernel stamps, verbose launch log) are compiled in
@@ -105,58 +105,7 @@ static inline int64_t e2_cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; 
 
 // ---- internal launchers (defined in the .hip files) ---------------------
 
-// Generic strided "valid" correlation as implicit GEMM on fp32 MFMA.
-//   out[n][oc][z][y][x] (+)= sum_ic sum_t Wp[dz][t][ic][oc] * in[n][ic][z+dz][y+ty][x+tx]
-// Wp is the PACKED weight image produced by e2i_pack_weights (flip folded in).
-struct IgemmArgs {
-  const float* in;
-  const float* wp;
-  float* out;
-  int N, Cin, Cout;
-  int kd, kh, kw;
-  int Do, Ho, Wo;          // output spatial
-  int64_t isN, isC, isZ, isY;
-  int64_t osN, osC, osZ, osY;
-  int ciP, coP;            // padded channel counts of the packed image
-  // upconv scatter mode: out channel oc' = co*R + r, stored at
-  // out[n][co][pz*z+rz][py*y+ry][px*x+rx]; R = pz*py*px (1 = off)
-  int upz, upy, upx;
-  // fused epilogue (conv forward of a layer that does not pool): out = act(conv + bias[oc]);
-  // relu writes -0.0 where the pre-activation was NEGATIVE and +0.0 where it was exactly
-  // zero, so that the backward can tell relu'(0) = 0.5 from 0 without the pre-activation
-  const float* bias = nullptr;
-  int act = 0;
-  // UpConv (upz * upy * upx > 1): bias[oc' / R] + activation in the epilogue IF the chosen
-  // kernel can (the pointwise GEMM, conv_pw.hip); *up_bias_done reports it, else the caller
-  // runs its bias / activation pass on the output
-  const float* up_bias = nullptr;
-  int up_act = 0;
-  int* up_bias_done = nullptr;
-  // gradient-mask epilogue (data gradient fused with the activation backward of the layer
-  // that produced this conv's input): out = conv * act'(gm_src), gm_dbias += column sums.
-  // gm_src: that layer's activated output with dense rows (nullptr = linear activation).
-  // e2i_igemm_conv reports in *gm_done whether the chosen kernel did it (else the caller
-  // runs the activation backward in place on the output).
-  int gm = 0;
-  const float* gm_src = nullptr;
-  int64_t gsN = 0, gsC = 0, gsZ = 0;
-  float* gm_dbias = nullptr;
-  const float* gm_bias = nullptr;   // non-null: gm_src is the PRE-activation, slope from gm_src + gm_bias[c]
-  int* gm_done = nullptr;
-  // split-K zero-fill of an output that is the interior of a zero-padded scratch buffer:
-  // the whole buffer may be filled flat (batched by the caller), nullptr = fill the view
-  float* fill_base = nullptr;
-  size_t fill_n = 0;
-  // data gradient: `in` is dy zero-padded by kd - 1 planes at both ends of z (the contract
-  // of e2_conv3d_dgrad*): the kernels skip the tap planes that read only that border
-  int zpad = 0;
-  // split-K with partial-sum stores instead of atomics (e2_conv3d_*_packed_parts): up to
-  // parts_max splits, split s stores to out + s * part_stride; *nparts receives the number
-  // of parts written (1: `out` holds the complete result).  parts_max <= 1: off.
-  int parts_max = 0;
-  int64_t part_stride = 0;
-  int* nparts = nullptr;
-};
+// IgemmArgs / WgradArgs and their builders: conv_host.hpp
 int e2i_igemm_conv(e2_ctx*, const IgemmArgs& a);
 int e2i_pw_conv(e2_ctx*, const IgemmArgs& a, int MT, int NT, int KC);   // 1x1x1 GEMM with LDS-staged weights (conv_pw.hip)
 
@@ -169,21 +118,6 @@ int e2i_pack_weights(e2_ctx*, const float* w, float* wp, int Cout, int Cin,
                      int ciP, int coP, int Rout, int Rin);
 void e2i_pack_dims(int cout, int cin, int* ciP, int* coP);
 
-struct WgradArgs {
-  const float* x;     // input activations view
-  const float* dy;    // output-gradient view (unpadded dims)
-  float* dw;          // [M][Cin*T] dense, accumulated atomically (pre-zeroed)
-  int N, Cin, Cout;
-  int kd, kh, kw;
-  int Do, Ho, Wo;
-  int64_t xsN, xsC, xsZ, xsY;
-  int64_t dsN, dsC, dsZ, dsY;
-  int flip;           // store tap index reversed
-  int upR;            // >1: rows are (co*R + r); store dw[co][col][r] (UpConv)
-  int accumulate;     // 1: dw += grad (caller zeroed it); 0: dw = grad
-  int dy_padded;      // 1: dy is the interior of a zero-padded buffer (row gaps hold
-                      //    zeros, >= 128 readable bytes follow its last element)
-};
 int e2i_upconv_dpre_s2d(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* yout, int pz,
                         int py, int px, int act, float* s2d, float* dbias);
 int e2i_wgrad_conv(e2_ctx*, const WgradArgs& a);

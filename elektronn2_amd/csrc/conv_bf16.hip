@@ -513,12 +513,8 @@ static int conv_bf16(e2_ctx* ctx, const e2_tensor5* in, const float* w, int nf, 
   const long units = (long)p.N * p.Do * p.nPT;
   const long grid = (units + 7) / 8 * 8 * p.nMT;
   E2_REQUIRE(grid < (1L << 31), "conv_bf16: grid too large");
-  {
-    int v[3];
-    const bool forced = sscanf(ctx->tiling[E2_TILING_IGEMM], "%d,%d,%d", &v[0], &v[1], &v[2]) == 3 && v[0] == 32;
-    e2_note_launch(ctx, "conv_bf16", forced ? E2_SRC_FORCED : (ctx->tiling[E2_TILING_IGEMM][0] ? E2_SRC_FALLBACK : E2_SRC_MODEL),
-                   "32,%d,%d", MB, NB);
-  }
+  const E2Tiling& t = ctx->tiling_v[E2_TILING_IGEMM];
+  e2_note_launch(ctx, "conv_bf16", e2_memory_src(e2_conv_bf16_forced(t), t), "32,%d,%d", MB, NB);
   if (MB == 1 && NB == 1) return launch<1, 1>(ctx, p, (int)grid, ldsb);
   if (MB == 1 && NB == 2) return launch<1, 2>(ctx, p, (int)grid, ldsb);
   if (MB == 2 && NB == 1) return launch<2, 1>(ctx, p, (int)grid, ldsb);
@@ -531,12 +527,29 @@ static int conv_bf16(e2_ctx* ctx, const e2_tensor5* in, const float* w, int nf, 
   return 2;
 }
 
-static void tile_from_ctx(const e2_ctx* ctx, int* MB, int* NB) {
-  *MB = 2; *NB = 2;
-  int v[3];
-  if (sscanf(ctx->tiling[E2_TILING_IGEMM], "%d,%d,%d", &v[0], &v[1], &v[2]) == 3 && v[0] == 32) {
-    *MB = v[1]; *NB = v[2];
-  }
+// The one implementation behind e2_conv3d_fwd_bf16* (mode 0: in = x) and e2_conv3d_dgrad_bf16*
+// (mode 1: in = the padded dy): the argument checks, the tile -- the forced "32,MB,NB", else
+// 2 x 2 -- and the launch.  in_ready: the caller hands over the bf16 copy of `in` (ext.xb), `in`
+// gives the shape only; need_keep: the entry point exists to fill xkeep.
+static int conv_bf16_entry(e2_ctx* ctx, const char* who, int mode, const e2_tensor5* in, const float* w,
+                           int rows, int kd, int kh, int kw, const float* bias, int act,
+                           const e2_tensor5* out, void* ws, size_t ws_bytes, void* xkeep = nullptr,
+                           size_t xkeep_bytes = 0, bool need_keep = false, bool in_ready = false,
+                           const CbExt& ext = CbExt()) {
+  const char* in_name = mode ? "dy_pad" : "x";
+  E2_REQUIRE(ctx && (w || ext.wb) && (xkeep || !need_keep), "%s: null argument", who);
+  E2_REQUIRE(in && in->n > 0 && in->c > 0 && in->d > 0 && in->h > 0 && in->w > 0 && (in->ptr || in_ready),
+             "%s: bad %s (null or empty tensor)", who, in_name);
+  char nm[96];
+  snprintf(nm, sizeof(nm), "%s %s", who, mode ? "dx" : "out");
+  if (int rc = view_ok(out, nm)) return rc;
+  E2_REQUIRE(!bias || act == E2_ACT_LIN || act == E2_ACT_RELU, "%s: bad act %d", who, act);
+  E2_REQUIRE(!in_ready || ext.xb, "%s: the ready-made copy of %s is missing", who, in_name);
+  const E2Tiling& t = ctx->tiling_v[E2_TILING_IGEMM];
+  const bool forced = e2_conv_bf16_forced(t);
+  const int MB = forced ? t.v[1] : 2, NB = forced ? t.v[2] : 2;
+  return conv_bf16(ctx, in, w, mode ? in->c : rows, mode ? rows : in->c, kd, kh, kw, mode, bias, act, out,
+                   ws, ws_bytes, MB, NB, xkeep, xkeep_bytes, ext);
 }
 
 }  // namespace
@@ -557,13 +570,7 @@ extern "C" size_t e2_conv3d_bf16_workspace_bytes(int n, int cin, int d, int h, i
 extern "C" int e2_conv3d_fwd_bf16(e2_ctx* ctx, const e2_tensor5* x, const float* w, int cout,
                                   int kd, int kh, int kw, const float* bias, int act,
                                   const e2_tensor5* out, void* ws, size_t ws_bytes) {
-  E2_REQUIRE(ctx && w, "conv3d_fwd_bf16: null argument");
-  if (int rc = view_ok(x, "conv3d_fwd_bf16 x")) return rc;
-  if (int rc = view_ok(out, "conv3d_fwd_bf16 out")) return rc;
-  E2_REQUIRE(!bias || act == E2_ACT_LIN || act == E2_ACT_RELU, "conv3d_fwd_bf16: bad act %d", act);
-  int MB, NB;
-  tile_from_ctx(ctx, &MB, &NB);
-  return conv_bf16(ctx, x, w, cout, x->c, kd, kh, kw, 0, bias, act, out, ws, ws_bytes, MB, NB);
+  return conv_bf16_entry(ctx, "conv3d_fwd_bf16", 0, x, w, cout, kd, kh, kw, bias, act, out, ws, ws_bytes);
 }
 
 extern "C" size_t e2_conv3d_bf16_xkeep_bytes(int n, int cin, int d, int h, int w, int kh, int kw) {
@@ -578,25 +585,14 @@ extern "C" int e2_conv3d_fwd_bf16_keep(e2_ctx* ctx, const e2_tensor5* x, const f
                                        int kd, int kh, int kw, const float* bias, int act,
                                        const e2_tensor5* out, void* ws, size_t ws_bytes,
                                        void* xkeep, size_t xkeep_bytes) {
-  E2_REQUIRE(ctx && w && xkeep, "conv3d_fwd_bf16_keep: null argument");
-  if (int rc = view_ok(x, "conv3d_fwd_bf16_keep x")) return rc;
-  if (int rc = view_ok(out, "conv3d_fwd_bf16_keep out")) return rc;
-  E2_REQUIRE(!bias || act == E2_ACT_LIN || act == E2_ACT_RELU, "conv3d_fwd_bf16_keep: bad act %d", act);
-  int MB, NB;
-  tile_from_ctx(ctx, &MB, &NB);
-  return conv_bf16(ctx, x, w, cout, x->c, kd, kh, kw, 0, bias, act, out, ws, ws_bytes, MB, NB,
-                   xkeep, xkeep_bytes);
+  return conv_bf16_entry(ctx, "conv3d_fwd_bf16_keep", 0, x, w, cout, kd, kh, kw, bias, act, out, ws, ws_bytes,
+                         xkeep, xkeep_bytes, true);
 }
 
 extern "C" int e2_conv3d_dgrad_bf16(e2_ctx* ctx, const e2_tensor5* dy_pad, const float* w, int cin,
                                     int kd, int kh, int kw, const e2_tensor5* dx, void* ws,
                                     size_t ws_bytes) {
-  E2_REQUIRE(ctx && w, "conv3d_dgrad_bf16: null argument");
-  if (int rc = view_ok(dy_pad, "conv3d_dgrad_bf16 dy_pad")) return rc;
-  if (int rc = view_ok(dx, "conv3d_dgrad_bf16 dx")) return rc;
-  int MB, NB;
-  tile_from_ctx(ctx, &MB, &NB);
-  return conv_bf16(ctx, dy_pad, w, dy_pad->c, cin, kd, kh, kw, 1, nullptr, 0, dx, ws, ws_bytes, MB, NB);
+  return conv_bf16_entry(ctx, "conv3d_dgrad_bf16", 1, dy_pad, w, cin, kd, kh, kw, nullptr, 0, dx, ws, ws_bytes);
 }
 
 // ---- operands made ahead of the launch (the producers' epilogues) ----------
@@ -636,31 +632,14 @@ extern "C" int e2_conv3d_fwd_bf16_ex(e2_ctx* ctx, const e2_tensor5* x, const flo
                                      const e2_tensor5* out, void* ws, size_t ws_bytes,
                                      void* xkeep, size_t xkeep_bytes, int x_ready, const void* wb,
                                      void* next_xb, int next_kg) {
-  E2_REQUIRE(ctx && (w || wb), "conv3d_fwd_bf16_ex: null argument");
-  E2_REQUIRE(x && x->n > 0 && x->c > 0 && x->d > 0 && x->h > 0 && x->w > 0 && (x->ptr || x_ready),
-             "conv3d_fwd_bf16_ex: bad x");
-  if (int rc = view_ok(out, "conv3d_fwd_bf16_ex out")) return rc;
-  E2_REQUIRE(!bias || act == E2_ACT_LIN || act == E2_ACT_RELU, "conv3d_fwd_bf16_ex: bad act %d", act);
-  E2_REQUIRE(!x_ready || xkeep, "conv3d_fwd_bf16_ex: x_ready names the copy in xkeep");
-  int MB, NB;
-  tile_from_ctx(ctx, &MB, &NB);
-  CbExt e;
-  e.xb = x_ready ? xkeep : nullptr; e.wb = wb; e.nxb = next_xb; e.nxKG = next_kg;
-  return conv_bf16(ctx, x, w, cout, x->c, kd, kh, kw, 0, bias, act, out, ws, ws_bytes, MB, NB,
-                   xkeep, xkeep_bytes, e);
+  return conv_bf16_entry(ctx, "conv3d_fwd_bf16_ex", 0, x, w, cout, kd, kh, kw, bias, act, out, ws, ws_bytes,
+                         xkeep, xkeep_bytes, false, x_ready != 0,
+                         CbExt{x_ready ? xkeep : nullptr, wb, next_xb, next_kg});
 }
 
 extern "C" int e2_conv3d_dgrad_bf16_ex(e2_ctx* ctx, const e2_tensor5* dy_pad, const float* w, int cin,
                                        int kd, int kh, int kw, const e2_tensor5* dx, void* ws,
                                        size_t ws_bytes, const void* dy_cl, const void* wb) {
-  E2_REQUIRE(ctx && (w || wb), "conv3d_dgrad_bf16_ex: null argument");
-  E2_REQUIRE(dy_pad && dy_pad->n > 0 && dy_pad->c > 0 && dy_pad->d > 0 && dy_pad->h > 0 && dy_pad->w > 0 &&
-                 (dy_pad->ptr || dy_cl), "conv3d_dgrad_bf16_ex: bad dy_pad");
-  if (int rc = view_ok(dx, "conv3d_dgrad_bf16_ex dx")) return rc;
-  int MB, NB;
-  tile_from_ctx(ctx, &MB, &NB);
-  CbExt e;
-  e.xb = dy_cl; e.wb = wb;
-  return conv_bf16(ctx, dy_pad, w, dy_pad->c, cin, kd, kh, kw, 1, nullptr, 0, dx, ws, ws_bytes, MB, NB,
-                   nullptr, 0, e);
+  return conv_bf16_entry(ctx, "conv3d_dgrad_bf16_ex", 1, dy_pad, w, cin, kd, kh, kw, nullptr, 0, dx, ws, ws_bytes,
+                         nullptr, 0, false, dy_cl != nullptr, CbExt{dy_cl, wb});
 }

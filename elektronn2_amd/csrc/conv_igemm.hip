@@ -344,17 +344,18 @@ static IgemmCfg choose_cfg(const e2_ctx* ctx, const IgemmArgs& a, int* ok) {
   const bool fast = has_fast_kw(a.kw);
   IgemmCfg best{0, 0, 0, 0};
   double bestCost = 1e300;
-  const char* force = ctx->tiling[E2_TILING_IGEMM];
-  if (force[0]) {
+  const E2Tiling& t = ctx->tiling_v[E2_TILING_IGEMM];
+  if (t.n) {
     IgemmCfg f{0, 0, 0, 0};
-    int v[8];
-    const int nf = sscanf(force, "%d,%d,%d,%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7]);
-    if (nf == 4) { f.MT = v[0]; f.NT = v[1]; f.CC = v[2]; f.SK = v[3]; *ok = 1; return f; }
-    if (nf == 3 && v[0] == 1) { f.kind = 1; f.MT = v[1]; f.NT = v[2]; *ok = 1; return f; }
-    if (nf == 5 && v[0] == 1) { f.kind = 1; f.MT = v[1]; f.NT = v[2]; f.KC = v[3]; *ok = 1; return f; }
-    if (nf == 8 && v[0] == 4) {
-      f.kind = 4; f.MT = v[1]; f.NT = v[2]; f.CC = v[3]; f.SK = v[4]; f.WM = v[5]; f.WN = v[6];
-      f.G = v[7]; *ok = 1; return f;
+    const int* v = t.v;
+    *ok = 1;
+    switch (e2_packed_form(t)) {
+      case E2_FORM_16x16x4: f.MT = v[0]; f.NT = v[1]; f.CC = v[2]; f.SK = v[3]; return f;
+      case E2_FORM_POINTWISE:                                       // ("1,MT,NT": KC 32)
+        f.kind = 1; f.MT = v[1]; f.NT = v[2]; if (t.n == 5) f.KC = v[3]; return f;
+      case E2_FORM_4x4x1:
+        f.kind = 4; f.MT = v[1]; f.NT = v[2]; f.CC = v[3]; f.SK = v[4]; f.WM = v[5]; f.WN = v[6];
+        f.G = v[7]; return f;
     }
     // a forced tiling this entry point cannot run ("32,MB,NB" belongs to e2_conv3d_*_bf16):
     // fail, never fall back silently (e2hip.h, e2_set_tiling)
@@ -455,6 +456,22 @@ static int igemm_zero_output(e2_ctx* ctx, const IgemmArgs& a) {
   return e2i_fill_view(ctx, &v, 0.f);
 }
 
+// what both MFMA kernels take straight from the launch's arguments; the tile geometry, the K
+// split and the epilogue switches are each kernel's own
+static void igemm_fill_common(IgemmP& p, const IgemmArgs& a) {
+  p.in = a.in; p.wp = a.wp; p.out = a.out;
+  p.Cin = a.Cin; p.Cout = a.Cout; p.kd = a.kd; p.kh = a.kh; p.kw = a.kw;
+  p.THW = a.kh * a.kw;
+  p.Do = a.Do; p.Ho = a.Ho; p.Wo = a.Wo; p.Q = a.Ho * a.Wo;
+  p.isN = a.isN; p.isC = a.isC; p.isZ = a.isZ; p.isY = a.isY;
+  p.osN = a.osN; p.osC = a.osC; p.osZ = a.osZ; p.osY = a.osY;
+  p.ciP = a.ciP; p.coP = a.coP;
+  p.Din = a.Do + a.kd - 1;
+  p.N = a.N;
+  p.upz = a.upz; p.upy = a.upy; p.upx = a.upx; p.zpad = a.zpad;
+  p.bias = a.bias; p.act = a.act;
+}
+
 // the 4x4x1-MFMA kernel (igemm4_core.hpp)
 static int igemm4_conv(e2_ctx* ctx, const IgemmArgs& a, const IgemmCfg& c) {
   E2_REQUIRE(has_fast_kw(a.kw), "igemm4: tap rows of %d have no instance", a.kw);
@@ -465,19 +482,11 @@ static int igemm4_conv(e2_ctx* ctx, const IgemmArgs& a, const IgemmCfg& c) {
              "igemm4: CC must be a multiple of 4 and of %d with an even number of steps per chunk", U);
   E2_REQUIRE(c.SK >= 1 && c.G >= 1 && c.G <= 8, "igemm4: SK must be >= 1, G in 1..8");
   IgemmP p;
-  p.in = a.in; p.wp = a.wp; p.out = a.out;
-  p.Cin = a.Cin; p.Cout = a.Cout; p.kd = a.kd; p.kh = a.kh; p.kw = a.kw;
-  p.THW = a.kh * a.kw;
-  p.Do = a.Do; p.Ho = a.Ho; p.Wo = a.Wo; p.Q = a.Ho * a.Wo;
-  p.isN = a.isN; p.isC = a.isC; p.isZ = a.isZ; p.isY = a.isY;
-  p.osN = a.osN; p.osC = a.osC; p.osZ = a.osZ; p.osY = a.osY;
-  p.ciP = a.ciP; p.coP = a.coP;
+  igemm_fill_common(p, a);
   const int BN = 64 * c.NT * c.WN, BM = 4 * c.MT * c.WM;
   p.Lpad = pad16mod32(span_lmax(a, BN) + 3);
   p.CC = c.CC;
-  p.Din = a.Do + a.kd - 1;
   p.dbg = 0;
-  p.N = a.N;
   p.nPT = e2_cdiv(p.Q, BN);
   p.nMT = e2_cdiv(a.Cout, BM);
   p.nChunkC = e2_cdiv(a.Cin, c.CC);
@@ -492,9 +501,8 @@ static int igemm4_conv(e2_ctx* ctx, const IgemmArgs& a, const IgemmCfg& c) {
   p.parts = parts4 ? 1 : 0; p.partStride = parts4 ? (long)a.part_stride : 0;
   if (a.nparts) *a.nparts = parts4 ? p.splitK : 1;
   p.atomic = (p.splitK > 1 && !parts4) ? 1 : 0;
-  p.upz = a.upz; p.upy = a.upy; p.upx = a.upx; p.zpad = a.zpad;
   p.bufFloats = c.CC * p.Lpad + 64;
-  p.stamps = nullptr; p.bias = a.bias; p.act = a.act; p.bf16 = 0; p.wide = 0;
+  p.stamps = nullptr; p.bf16 = 0; p.wide = 0;
   // channels past Cin are staged as copies of the last one: their weight rows must exist and be zero
   E2_REQUIRE(p.nChunkC * c.CC <= a.ciP, "igemm4: CC=%d pads Cin=%d beyond the packed image", c.CC, a.Cin);
   // a wave reads 64-channel rows starting at its first channel
@@ -520,6 +528,138 @@ static int igemm4_conv(e2_ctx* ctx, const IgemmArgs& a, const IgemmCfg& c) {
   }
 }
 
+// debug (E2_IGEMM_STAMPS): per-work-group timeline stamps of the 16x16x4 kernel's fast path
+static unsigned long long* g_stamp_buf = nullptr;
+static int igemm_stamps_begin(e2_ctx* ctx, long grid, unsigned long long** stamps) {
+  if (!g_stamp_buf) E2_CHECK_HIP(hipMalloc(&g_stamp_buf, 8 * sizeof(unsigned long long) * 65536));
+  E2_REQUIRE(grid <= 65536, "igemm stamps: grid too large");
+  E2_CHECK_HIP(hipMemsetAsync(g_stamp_buf, 0, 8 * sizeof(unsigned long long) * grid, ctx->stream));
+  *stamps = g_stamp_buf;
+  return 0;
+}
+// ... read back and printed after a sync
+static int igemm_stamps_report(e2_ctx* ctx, long grid) {
+  std::vector<unsigned long long> h(8 * grid);
+  E2_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  E2_CHECK_HIP(hipMemcpy(h.data(), g_stamp_buf, 8 * sizeof(unsigned long long) * grid, hipMemcpyDeviceToHost));
+  unsigned long long r0 = ~0ull, r1 = 0;
+  double s_first = 0, s_loop = 0, s_epi = 0, s_tot = 0, max_tot = 0;
+  for (long b = 0; b < grid; ++b) {
+    const unsigned long long* s = &h[8 * b];
+    r0 = std::min(r0, s[0]); r1 = std::max(r1, s[5]);
+    s_first += (double)(s[2] - s[1]); s_loop += (double)(s[3] - s[2]);
+    s_epi += (double)(s[4] - s[3]); s_tot += (double)(s[4] - s[1]);
+    max_tot = std::max(max_tot, (double)(s[4] - s[1]));
+  }
+  double last_start = 0;
+  for (long b = 0; b < grid; ++b) last_start = std::max(last_start, (double)(h[8 * b] - r0));
+  fprintf(stderr, "[e2 stamps] grid=%ld  span(first start..last end)=%.2f us  last block start +%.2f us | per block (cycles, mean): "
+          "to first barrier %.0f, main loop %.0f, epilogue %.0f, total %.0f (max %.0f)\n",
+          grid, (double)(r1 - r0) * 0.01, last_start * 0.01, s_first / grid, s_loop / grid, s_epi / grid,
+          s_tot / grid, max_tot);
+  // in-kernel clock (MI355X_MICROARCH.md "DVFS give-back" item 6): shader cycles
+  // (s_memtime) per 100 MHz tick (s_memrealtime) between a work-group's first and last
+  // stamp, median over the work-groups
+  std::vector<double> clk;
+  for (long b = 0; b < grid; ++b) {
+    const unsigned long long* s = &h[8 * b];
+    if (s[5] > s[0]) clk.push_back((double)(s[4] - s[1]) / (double)(s[5] - s[0]) * 0.1);
+  }
+  if (!clk.empty()) {
+    std::sort(clk.begin(), clk.end());
+    fprintf(stderr, "[e2 stamps] in-kernel clock: median %.3f GHz (min %.3f, max %.3f) over %zu work-groups\n",
+            clk[clk.size() / 2], clk.front(), clk.back(), clk.size());
+  }
+  return 0;
+}
+
+// the instance of the 16x16x4 kernel for a tap-row width (generic: any other width, f32 only)
+static int igemm16_launch(e2_ctx* ctx, const IgemmP& p, int MT, int NT, int GU, int grid, size_t lds) {
+  if (p.bf16) {
+    switch (p.kw) {
+      case 1: return e2i_igemm_launch_k1_bf(ctx, p, MT, NT, GU, grid, lds);
+      case 3: return e2i_igemm_launch_k3_bf(ctx, p, MT, NT, GU, grid, lds);
+      case 4: return e2i_igemm_launch_k4_bf(ctx, p, MT, NT, GU, grid, lds);
+      default: return e2i_igemm_launch_k5_bf(ctx, p, MT, NT, GU, grid, lds);
+    }
+  }
+  switch (p.kw) {
+    case 1: return e2i_igemm_launch_k1(ctx, p, MT, NT, GU, grid, lds);
+    case 3: return e2i_igemm_launch_k3(ctx, p, MT, NT, GU, grid, lds);
+    case 4: return e2i_igemm_launch_k4(ctx, p, MT, NT, GU, grid, lds);
+    case 5: return e2i_igemm_launch_k5(ctx, p, MT, NT, GU, grid, lds);
+    default: return e2i_igemm_launch_generic(ctx, p, MT, NT, grid, lds);
+  }
+}
+
+// the 16x16x4-MFMA kernel (igemm_core.hpp)
+static int igemm16_conv(e2_ctx* ctx, const IgemmArgs& a, const IgemmCfg& c) {
+  const bool fast = has_fast_kw(a.kw);
+  // the gradient-mask epilogue lives in the specialised-width 16x16x4 kernel
+  const bool gm = a.gm && fast && a.upz * a.upy * a.upx == 1 && a.Wo >= 4;
+  E2_REQUIRE(c.CC >= 4 && c.CC % 4 == 0 && c.CC <= (fast ? 64 : 32),
+             "igemm: CC must be a multiple of 4, at most %d", fast ? 64 : 32);
+  E2_REQUIRE(c.NT == 1 || c.NT == 2 || c.NT == 4, "igemm: NT must be 1, 2 or 4");
+  E2_REQUIRE(c.SK >= 1, "igemm: SK must be >= 1");
+  IgemmP p;
+  igemm_fill_common(p, a);
+  const int BN = 64 * c.NT;
+  p.Lpad = span_lpad(a, BN);
+  p.CC = c.CC;
+  p.dbg = e2_dbg_env_int("E2_IGEMM_DBG");
+  p.nPT = e2_cdiv(p.Q, BN);
+  p.nMT = e2_cdiv(e2_cdiv(a.Cout, 16), c.MT);
+  p.nChunkC = e2_cdiv(a.Cin, c.CC);
+  // K splits (unlike the 4x4x1 kernel's: clipped to parts_max only where parts are possible, and
+  // not rebalanced over the chunks)
+  p.splitK = a.bias ? 1 : std::min(c.SK, a.kd * p.nChunkC);     // the fused epilogue cannot split K
+  const bool parts = a.parts_max > 1 && a.upz * a.upy * a.upx == 1;
+  if (parts) p.splitK = std::min(p.splitK, a.parts_max);
+  p.parts = (parts && p.splitK > 1) ? 1 : 0;
+  p.partStride = p.parts ? (long)a.part_stride : 0;
+  if (a.nparts) *a.nparts = p.parts ? p.splitK : 1;
+  p.atomic = (p.splitK > 1 && !p.parts) ? 1 : 0;
+  p.bufFloats = (int)buf_floats(a, c.MT, BN, c.CC);
+  E2_REQUIRE(p.nMT * 16 * c.MT <= a.coP, "igemm: packed coP too small");
+  if (fast) E2_REQUIRE(((a.Cin + 15) / 16) * 16 <= a.ciP, "igemm: packed ciP too small");
+  else E2_REQUIRE(p.nChunkC * c.CC <= a.ciP, "igemm: packed ciP too small");
+  size_t lds = 2 * (size_t)p.bufFloats * 4;
+  E2_REQUIRE(lds <= 160 * 1024, "igemm: forced tiling needs %zu B of LDS", lds);
+  // wide epilogue (fast path): dense output rows, plain stores
+  const size_t tile_lds = (size_t)4 * 16 * c.MT * (16 * c.NT + 4) * 4 + (gm ? 4 * 16 * c.MT * 4 : 0);
+  p.wide = (fast && (p.splitK == 1 || p.parts) && a.upz * a.upy * a.upx == 1 && (a.osY == a.Wo || a.Wo >= 4) &&
+            std::max(lds, tile_lds) <= 160 * 1024 && !e2_dbg_env("E2_IGEMM_NARROW")) ? 1 : 0;
+  if (p.wide) lds = std::max(lds, tile_lds);
+  if (gm) {
+    p.gm = 1; p.gm_src = a.gm_src; p.gsN = a.gsN; p.gsC = a.gsC; p.gsZ = a.gsZ;
+    p.gm_dbias = a.gm_dbias; p.gm_bias = a.gm_bias;
+    if (a.gm_done) *a.gm_done = 1;
+  }
+  E2_REQUIRE(!a.bias || p.wide, "igemm: the fused bias/act epilogue needs dense output rows, a "
+             "specialised kernel width and %zu B of LDS", tile_lds);
+  const long grid = (long)a.N * p.splitK * p.nMT * p.Do * p.nPT;
+  E2_REQUIRE(grid < (1L << 31), "igemm: grid too large");
+  ctx->last_fill_ptr = nullptr; ctx->last_fill_n = 0;
+  if (p.atomic)
+    if (int rc = igemm_zero_output(ctx, a)) return rc;
+  p.stamps = nullptr;
+  const bool want_stamps = e2_dbg_env("E2_IGEMM_STAMPS") != nullptr && fast && !ctx->capturing;
+  if (want_stamps)
+    if (int rc = igemm_stamps_begin(ctx, grid, &p.stamps)) return rc;
+  // 1x1 taps: four channel groups per pipeline step when the chunk allows it
+  const int GU = (fast && p.THW == 1 && c.CC % 16 == 0) ? 4 : 1;
+  if (e2_dbg_env("E2_VERBOSE"))
+    fprintf(stderr, "[e2] igemm%s Cin=%d Cout=%d k=%d,%d,%d out=%d,%d,%d MT=%d NT=%d CC=%d SK=%d GU=%d grid=%ld lds=%zu\n",
+            (ctx->mfma_bf16 && fast) ? "(bf16)" : "", a.Cin, a.Cout, a.kd, a.kh, a.kw, a.Do, a.Ho, a.Wo, c.MT, c.NT, c.CC, p.splitK, GU, grid, lds);
+  p.bf16 = (ctx->mfma_bf16 && fast) ? 1 : 0;     // the generic-width kernel stays f32
+  const int rc = igemm16_launch(ctx, p, c.MT, c.NT, GU, (int)grid, lds);
+  if (rc == 0 && want_stamps) return igemm_stamps_report(ctx, grid);
+  return rc;
+}
+
+// One launch: the tiling (forced or the cost model's), the note for e2_last_launch -- BEFORE the
+// chosen kernel's own requirements, so that a launch that fails them has still overwritten it --
+// and the kernel family's launcher.
 int e2i_igemm_conv(e2_ctx* ctx, const IgemmArgs& a) {
   E2_REQUIRE(a.Do > 0 && a.Ho > 0 && a.Wo > 0 && a.Cin > 0 && a.Cout > 0,
              "igemm: empty problem");
@@ -534,7 +674,7 @@ int e2i_igemm_conv(e2_ctx* ctx, const IgemmArgs& a) {
   if (a.gm_done) *a.gm_done = 0;
   if (a.up_bias_done) *a.up_bias_done = 0;
   if (a.nparts) *a.nparts = 1;
-  const int src = ctx->tiling[E2_TILING_IGEMM][0] ? E2_SRC_FORCED : E2_SRC_MODEL;   // (no fallback here)
+  const int src = ctx->tiling_v[E2_TILING_IGEMM].n ? E2_SRC_FORCED : E2_SRC_MODEL;   // (no fallback here)
   if (c.kind == 4) {
     e2_note_launch(ctx, "igemm4", src, "4,%d,%d,%d,%d,%d,%d,%d", c.MT, c.NT, c.CC, c.SK, c.WM, c.WN, c.G);
     return igemm4_conv(ctx, a, c);
@@ -544,128 +684,7 @@ int e2i_igemm_conv(e2_ctx* ctx, const IgemmArgs& a) {
     e2_note_launch(ctx, "pw_gemm", src, "1,%d,%d,%d,0", c.MT, c.NT, c.KC);
     return e2i_pw_conv(ctx, a, c.MT, c.NT, c.KC);
   }
-  const bool fast = has_fast_kw(a.kw);
-  e2_note_launch(ctx, !fast ? "igemm_generic" : (ctx->mfma_bf16 ? "igemm_bf16r" : "igemm"), src, "%d,%d,%d,%d",
-                 c.MT, c.NT, c.CC, c.SK);
-  // the gradient-mask epilogue lives in the specialised-width 16x16x4 kernel
-  const bool gm = a.gm && fast && a.upz * a.upy * a.upx == 1 && a.Wo >= 4;
-  E2_REQUIRE(c.CC >= 4 && c.CC % 4 == 0 && c.CC <= (fast ? 64 : 32),
-             "igemm: CC must be a multiple of 4, at most %d", fast ? 64 : 32);
-  E2_REQUIRE(c.NT == 1 || c.NT == 2 || c.NT == 4, "igemm: NT must be 1, 2 or 4");
-  E2_REQUIRE(c.SK >= 1, "igemm: SK must be >= 1");
-  IgemmP p;
-  p.in = a.in; p.wp = a.wp; p.out = a.out;
-  p.Cin = a.Cin; p.Cout = a.Cout; p.kd = a.kd; p.kh = a.kh; p.kw = a.kw;
-  p.THW = a.kh * a.kw;
-  p.Do = a.Do; p.Ho = a.Ho; p.Wo = a.Wo; p.Q = a.Ho * a.Wo;
-  p.isN = a.isN; p.isC = a.isC; p.isZ = a.isZ; p.isY = a.isY;
-  p.osN = a.osN; p.osC = a.osC; p.osZ = a.osZ; p.osY = a.osY;
-  p.ciP = a.ciP; p.coP = a.coP;
-  const int BN = 64 * c.NT;
-  p.Lpad = span_lpad(a, BN);
-  p.CC = c.CC;
-  p.Din = a.Do + a.kd - 1;
-  p.dbg = e2_dbg_env_int("E2_IGEMM_DBG");
-  p.N = a.N;
-  p.nPT = e2_cdiv(p.Q, BN);
-  p.nMT = e2_cdiv(e2_cdiv(a.Cout, 16), c.MT);
-  p.nChunkC = e2_cdiv(a.Cin, c.CC);
-  p.splitK = a.bias ? 1 : std::min(c.SK, a.kd * p.nChunkC);     // the fused epilogue cannot split K
-  const bool parts = a.parts_max > 1 && a.upz * a.upy * a.upx == 1;
-  if (parts) p.splitK = std::min(p.splitK, a.parts_max);
-  p.parts = (parts && p.splitK > 1) ? 1 : 0;
-  p.partStride = p.parts ? (long)a.part_stride : 0;
-  if (a.nparts) *a.nparts = p.parts ? p.splitK : 1;
-  p.atomic = (p.splitK > 1 && !p.parts) ? 1 : 0;
-  p.upz = a.upz; p.upy = a.upy; p.upx = a.upx; p.zpad = a.zpad;
-  p.bufFloats = (int)buf_floats(a, c.MT, BN, c.CC);
-  E2_REQUIRE(p.nMT * 16 * c.MT <= a.coP, "igemm: packed coP too small");
-  if (fast) E2_REQUIRE(((a.Cin + 15) / 16) * 16 <= a.ciP, "igemm: packed ciP too small");
-  else E2_REQUIRE(p.nChunkC * c.CC <= a.ciP, "igemm: packed ciP too small");
-  size_t lds = 2 * (size_t)p.bufFloats * 4;
-  E2_REQUIRE(lds <= 160 * 1024, "igemm: forced tiling needs %zu B of LDS", lds);
-  // wide epilogue (fast path): dense output rows, plain stores
-  const size_t tile_lds = (size_t)4 * 16 * c.MT * (16 * c.NT + 4) * 4 + (gm ? 4 * 16 * c.MT * 4 : 0);
-  p.wide = (fast && (p.splitK == 1 || p.parts) && a.upz * a.upy * a.upx == 1 && (a.osY == a.Wo || a.Wo >= 4) &&
-            std::max(lds, tile_lds) <= 160 * 1024 && !e2_dbg_env("E2_IGEMM_NARROW")) ? 1 : 0;
-  if (p.wide) lds = std::max(lds, tile_lds);
-  p.bias = a.bias; p.act = a.act;
-  if (gm) {
-    p.gm = 1; p.gm_src = a.gm_src; p.gsN = a.gsN; p.gsC = a.gsC; p.gsZ = a.gsZ;
-    p.gm_dbias = a.gm_dbias; p.gm_bias = a.gm_bias;
-    if (a.gm_done) *a.gm_done = 1;
-  }
-  E2_REQUIRE(!a.bias || p.wide, "igemm: the fused bias/act epilogue needs dense output rows, a "
-             "specialised kernel width and %zu B of LDS", tile_lds);
-  const long grid = (long)a.N * p.splitK * p.nMT * p.Do * p.nPT;
-  E2_REQUIRE(grid < (1L << 31), "igemm: grid too large");
-  ctx->last_fill_ptr = nullptr; ctx->last_fill_n = 0;
-  if (p.atomic)
-    if (int rc = igemm_zero_output(ctx, a)) return rc;
-  // debug: per-work-group timeline stamps (fast path only), printed after a sync
-  p.stamps = nullptr;
-  static unsigned long long* stamp_buf = nullptr;
-  const bool want_stamps = e2_dbg_env("E2_IGEMM_STAMPS") != nullptr && fast && !ctx->capturing;
-  if (want_stamps) {
-    if (!stamp_buf) E2_CHECK_HIP(hipMalloc(&stamp_buf, 8 * sizeof(unsigned long long) * 65536));
-    E2_REQUIRE(grid <= 65536, "igemm stamps: grid too large");
-    E2_CHECK_HIP(hipMemsetAsync(stamp_buf, 0, 8 * sizeof(unsigned long long) * grid, ctx->stream));
-    p.stamps = stamp_buf;
-  }
-  // 1x1 taps: four channel groups per pipeline step when the chunk allows it
-  const int GU = (fast && p.THW == 1 && c.CC % 16 == 0) ? 4 : 1;
-  if (e2_dbg_env("E2_VERBOSE"))
-    fprintf(stderr, "[e2] igemm%s Cin=%d Cout=%d k=%d,%d,%d out=%d,%d,%d MT=%d NT=%d CC=%d SK=%d GU=%d grid=%ld lds=%zu\n",
-            (ctx->mfma_bf16 && fast) ? "(bf16)" : "", a.Cin, a.Cout, a.kd, a.kh, a.kw, a.Do, a.Ho, a.Wo, c.MT, c.NT, c.CC, p.splitK, GU, grid, lds);
-  int rc;
-  p.bf16 = (ctx->mfma_bf16 && fast) ? 1 : 0;     // the generic-width kernel stays f32
-  if (p.bf16) {
-    switch (a.kw) {
-      case 1: rc = e2i_igemm_launch_k1_bf(ctx, p, c.MT, c.NT, GU, (int)grid, lds); break;
-      case 3: rc = e2i_igemm_launch_k3_bf(ctx, p, c.MT, c.NT, GU, (int)grid, lds); break;
-      case 4: rc = e2i_igemm_launch_k4_bf(ctx, p, c.MT, c.NT, GU, (int)grid, lds); break;
-      default: rc = e2i_igemm_launch_k5_bf(ctx, p, c.MT, c.NT, GU, (int)grid, lds); break;
-    }
-  } else
-  switch (a.kw) {
-    case 1: rc = e2i_igemm_launch_k1(ctx, p, c.MT, c.NT, GU, (int)grid, lds); break;
-    case 3: rc = e2i_igemm_launch_k3(ctx, p, c.MT, c.NT, GU, (int)grid, lds); break;
-    case 4: rc = e2i_igemm_launch_k4(ctx, p, c.MT, c.NT, GU, (int)grid, lds); break;
-    case 5: rc = e2i_igemm_launch_k5(ctx, p, c.MT, c.NT, GU, (int)grid, lds); break;
-    default: rc = e2i_igemm_launch_generic(ctx, p, c.MT, c.NT, (int)grid, lds);
-  }
-  if (rc == 0 && want_stamps) {
-    std::vector<unsigned long long> h(8 * grid);
-    E2_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    E2_CHECK_HIP(hipMemcpy(h.data(), stamp_buf, 8 * sizeof(unsigned long long) * grid, hipMemcpyDeviceToHost));
-    unsigned long long r0 = ~0ull, r1 = 0;
-    double s_first = 0, s_loop = 0, s_epi = 0, s_tot = 0, max_tot = 0;
-    for (long b = 0; b < grid; ++b) {
-      const unsigned long long* s = &h[8 * b];
-      r0 = std::min(r0, s[0]); r1 = std::max(r1, s[5]);
-      s_first += (double)(s[2] - s[1]); s_loop += (double)(s[3] - s[2]);
-      s_epi += (double)(s[4] - s[3]); s_tot += (double)(s[4] - s[1]);
-      max_tot = std::max(max_tot, (double)(s[4] - s[1]));
-    }
-    double last_start = 0;
-    for (long b = 0; b < grid; ++b) last_start = std::max(last_start, (double)(h[8 * b] - r0));
-    fprintf(stderr, "[e2 stamps] grid=%ld  span(first start..last end)=%.2f us  last block start +%.2f us | per block (cycles, mean): "
-            "to first barrier %.0f, main loop %.0f, epilogue %.0f, total %.0f (max %.0f)\n",
-            grid, (double)(r1 - r0) * 0.01, last_start * 0.01, s_first / grid, s_loop / grid, s_epi / grid,
-            s_tot / grid, max_tot);
-    // in-kernel clock (MI355X_MICROARCH.md "DVFS give-back" item 6): shader cycles
-    // (s_memtime) per 100 MHz tick (s_memrealtime) between a work-group's first and last
-    // stamp, median over the work-groups
-    std::vector<double> clk;
-    for (long b = 0; b < grid; ++b) {
-      const unsigned long long* s = &h[8 * b];
-      if (s[5] > s[0]) clk.push_back((double)(s[4] - s[1]) / (double)(s[5] - s[0]) * 0.1);
-    }
-    if (!clk.empty()) {
-      std::sort(clk.begin(), clk.end());
-      fprintf(stderr, "[e2 stamps] in-kernel clock: median %.3f GHz (min %.3f, max %.3f) over %zu work-groups\n",
-              clk[clk.size() / 2], clk.front(), clk.back(), clk.size());
-    }
-  }
-  return rc;
+  e2_note_launch(ctx, !has_fast_kw(a.kw) ? "igemm_generic" : (ctx->mfma_bf16 ? "igemm_bf16r" : "igemm"), src,
+                 "%d,%d,%d,%d", c.MT, c.NT, c.CC, c.SK);
+  return igemm16_conv(ctx, a, c);
 }

@@ -438,12 +438,12 @@ static WCfg choose_wcfg(const e2_ctx* ctx, const WgradArgs& a, int* ok, int* src
   WCfg best{0, 0, 0, 0, 0};
   double bestCost = 1e300;
   const double dw_bytes = 4.0 * a.Cout * (double)NTOT;
-  const char* force = ctx->tiling[E2_TILING_WGRAD];
+  const E2Tiling& t = ctx->tiling_v[E2_TILING_WGRAD];
   *src = E2_SRC_MODEL;
-  if (force[0]) {
+  if (t.n) {
     *src = E2_SRC_FALLBACK;           // ... unless one of the returns below honours the string
-    WCfg f{0, 0, 0, 0, 0};
-    if (sscanf(force, "%d,%d,%d,%d,%d", &f.MT, &f.NT, &f.WK, &f.BP, &f.PS) == 5) {
+    if (e2_wgrad_candidate(t)) {
+      const WCfg f{t.v[0], t.v[1], t.v[2], t.v[3], t.v[4]};
       // "MT,NT,7,0,S" names the K-contiguous 1x1x1 GEMM (conv_pw_wgrad.hip), which takes dense
       // channel planes and f32 mode only.  The tuning keys hold the row pitch, not the plane
       // pitch: a view that keeps the rows but not the planes (a crop along the second spatial

@@ -634,6 +634,30 @@ size_t e2i_wgrad_direct_buf_floats(const WgradArgs& a, int NT, int BP, int WK) {
   return (size_t)(BP + 256) + (size_t)d_maxspans(a, 16 * NT * (4 / WK)) * e2i_wgrad_direct_lpad(a, BP) + 64;
 }
 
+// debug (E2_WGRAD_STAMPS): the work-groups' timeline stamps, read back and printed after a sync;
+// per = tiles per work-group, ideal = the main loop's MFMA cycles
+static unsigned long long* g_wstamp_buf = nullptr;
+static int wgrad_stamps_report(e2_ctx* ctx, long grid, int per, double ideal) {
+  std::vector<unsigned long long> h(8 * grid);
+  E2_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  E2_CHECK_HIP(hipMemcpy(h.data(), g_wstamp_buf, 8 * sizeof(unsigned long long) * grid, hipMemcpyDeviceToHost));
+  unsigned long long r0 = ~0ull, r1 = 0;
+  double s_first = 0, s_loop = 0, s_epi = 0, s_tot = 0, max_tot = 0, last_start = 0;
+  for (long b = 0; b < grid; ++b) {
+    const unsigned long long* s = &h[8 * b];
+    r0 = std::min(r0, s[0]); r1 = std::max(r1, s[5]);
+    s_first += (double)(s[2] - s[1]); s_loop += (double)(s[3] - s[2]);
+    s_epi += (double)(s[4] - s[3]); s_tot += (double)(s[4] - s[1]);
+    max_tot = std::max(max_tot, (double)(s[4] - s[1]));
+  }
+  for (long b = 0; b < grid; ++b) last_start = std::max(last_start, (double)(h[8 * b] - r0));
+  fprintf(stderr, "[e2 wgrad stamps] grid=%ld tiles/wg=%d  span=%.2f us  last start +%.2f us | per wg (cycles, mean): "
+          "to first quad %.0f, main loop %.0f (ideal %.0f), flush %.0f, total %.0f (max %.0f)\n",
+          grid, per, (double)(r1 - r0) * 0.01, last_start * 0.01, s_first / grid, s_loop / grid,
+          ideal, s_epi / grid, s_tot / grid, max_tot);
+  return 0;
+}
+
 int e2i_wgrad_direct(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int BP, int PS, int WK, int xcd) {
   E2_REQUIRE(BP == 128 || BP == 256, "wgrad(direct): BP must be 128 or 256");
   E2_REQUIRE(WK == 1 || (WK == 4 && (NT == 2 || NT == 4)), "wgrad(direct): WK=4 needs NT 2 or 4");
@@ -671,12 +695,11 @@ int e2i_wgrad_direct(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int BP, in
   const long pairs = (long)p.nMT * p.nPS * p.nNT;
   const long grid = p.xcd ? ((pairs + 7) / 8) * 8 : pairs;
   p.stamps = nullptr;
-  static unsigned long long* stamp_buf = nullptr;
   const bool want_stamps = e2_dbg_env("E2_WGRAD_STAMPS") != nullptr && !ctx->capturing && grid <= 65536;
   if (want_stamps) {
-    if (!stamp_buf) E2_CHECK_HIP(hipMalloc(&stamp_buf, 8 * sizeof(unsigned long long) * 65536));
-    E2_CHECK_HIP(hipMemsetAsync(stamp_buf, 0, 8 * sizeof(unsigned long long) * grid, ctx->stream));
-    p.stamps = stamp_buf;
+    if (!g_wstamp_buf) E2_CHECK_HIP(hipMalloc(&g_wstamp_buf, 8 * sizeof(unsigned long long) * 65536));
+    E2_CHECK_HIP(hipMemsetAsync(g_wstamp_buf, 0, 8 * sizeof(unsigned long long) * grid, ctx->stream));
+    p.stamps = g_wstamp_buf;
   }
   E2_REQUIRE(grid < (1L << 31), "wgrad: grid too large");
   if (!a.accumulate)
@@ -695,24 +718,8 @@ int e2i_wgrad_direct(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int BP, in
     default: e2_set_error("wgrad(direct): no instance MT=%d", MT);
   }
   if (rc == 0 && want_stamps) {
-    std::vector<unsigned long long> h(8 * grid);
-    E2_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    E2_CHECK_HIP(hipMemcpy(h.data(), stamp_buf, 8 * sizeof(unsigned long long) * grid, hipMemcpyDeviceToHost));
-    unsigned long long r0 = ~0ull, r1 = 0;
-    double s_first = 0, s_loop = 0, s_epi = 0, s_tot = 0, max_tot = 0, last_start = 0;
-    for (long b = 0; b < grid; ++b) {
-      const unsigned long long* s = &h[8 * b];
-      r0 = std::min(r0, s[0]); r1 = std::max(r1, s[5]);
-      s_first += (double)(s[2] - s[1]); s_loop += (double)(s[3] - s[2]);
-      s_epi += (double)(s[4] - s[3]); s_tot += (double)(s[4] - s[1]);
-      max_tot = std::max(max_tot, (double)(s[4] - s[1]));
-    }
-    for (long b = 0; b < grid; ++b) last_start = std::max(last_start, (double)(h[8 * b] - r0));
     const int per = (p.tilesTotal + p.nPS - 1) / p.nPS;
-    fprintf(stderr, "[e2 wgrad stamps] grid=%ld tiles/wg=%d  span=%.2f us  last start +%.2f us | per wg (cycles, mean): "
-            "to first quad %.0f, main loop %.0f (ideal %.0f), flush %.0f, total %.0f (max %.0f)\n",
-            grid, per, (double)(r1 - r0) * 0.01, last_start * 0.01, s_first / grid, s_loop / grid,
-            (double)per * (BP / 4 / WK) * MT * NT * 32.0, s_epi / grid, s_tot / grid, max_tot);
+    return wgrad_stamps_report(ctx, grid, per, (double)per * (BP / 4 / WK) * MT * NT * 32.0);
   }
   return rc;
 }

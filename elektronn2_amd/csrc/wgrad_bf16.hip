@@ -409,7 +409,9 @@ extern "C" size_t e2_conv3d_wgrad_bf16_workspace_bytes(int n, int cin, int d, in
 // return.  With all three the conversion pass disappears and ws may be NULL.
 static int wgrad_bf16(e2_ctx* ctx, const e2_tensor5* x, const void* xcl_ext, int kgs_ext,
                       const e2_tensor5* dy, float* dw, int kd, int kh, int kw, int accumulate,
-                      void* ws, size_t ws_bytes, const void* dyc_ext = nullptr, float* dwt_ext = nullptr) {
+                      void* ws, size_t ws_bytes, const void* dyc_ext = nullptr, float* dwt_ext = nullptr,
+                      bool need_xcl = false) {
+  E2_REQUIRE(xcl_ext || !need_xcl, "conv3d_wgrad_bf16_xcl: null copy");
   E2_REQUIRE(ctx && dw, "conv3d_wgrad_bf16: null argument");
   if (xcl_ext) {
     E2_REQUIRE(x && x->n > 0 && x->c > 0 && x->d > 0 && x->h > 0 && x->w > 0, "conv3d_wgrad_bf16_xcl: bad x shape");
@@ -433,11 +435,9 @@ static int wgrad_bf16(e2_ctx* ctx, const e2_tensor5* x, const void* xcl_ext, int
   E2_REQUIRE(all_ext || ((uintptr_t)ws & 15) == 0, "conv3d_wgrad_bf16: workspace must be 16-byte aligned");
   E2_REQUIRE(((uintptr_t)dwt_ext & 15) == 0, "conv3d_wgrad_bf16: the sum buffer must be 16-byte aligned");
   int MB = 2, NB = 0, S = 0, rows = Cin <= 64 ? 1 : 0;
-  {
-    int v[5];
-    if (sscanf(ctx->tiling[E2_TILING_WGRAD], "%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4]) == 5 &&
-        v[0] == 32) { MB = v[1]; NB = v[2]; rows = v[3] != 0; S = v[4]; }
-  }
+  const E2Tiling& t = ctx->tiling_v[E2_TILING_WGRAD];
+  const bool forced = e2_wgrad_bf16_forced(t);                 // "32,MB,NB,R,S"
+  if (forced) { MB = t.v[1]; NB = t.v[2]; rows = t.v[3] != 0; S = t.v[4]; }
   if (NB <= 0) NB = kw >= 4 ? 4 : (kw == 3 ? 3 : kw);        // taps of a kernel row per wave
   E2_REQUIRE((MB == 1 || MB == 2) && NB >= 1 && NB <= 4, "conv3d_wgrad_bf16: MB 1..2, NB 1..4");
   __bf16* xcl = xcl_ext ? const_cast<__bf16*>(reinterpret_cast<const __bf16*>(xcl_ext))
@@ -495,12 +495,7 @@ static int wgrad_bf16(e2_ctx* ctx, const e2_tensor5* x, const void* xcl_ext, int
   const long grid = 8L * p.perXcd;                                 // (work-groups past the last one exit)
   E2_REQUIRE(grid < (1L << 31), "conv3d_wgrad_bf16: grid too large");
   E2_REQUIRE((size_t)T * 33 * 4 <= 64 * 1024, "conv3d_wgrad_bf16: %d taps exceed the output pass's LDS tile", T);
-  {
-    int v[5];
-    const bool forced = sscanf(ctx->tiling[E2_TILING_WGRAD], "%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4]) == 5 && v[0] == 32;
-    e2_note_launch(ctx, "wgrad_bf16", forced ? E2_SRC_FORCED : (ctx->tiling[E2_TILING_WGRAD][0] ? E2_SRC_FALLBACK : E2_SRC_MODEL),
-                   "32,%d,%d,%d,%d", MB, NB, rows ? 1 : 0, S);
-  }
+  e2_note_launch(ctx, "wgrad_bf16", e2_memory_src(forced, t), "32,%d,%d,%d,%d", MB, NB, rows ? 1 : 0, S);
   int rc = 2;
 #define E2_L(M, N_) if (MB == M && NB == N_) rc = rows ? launch<M, N_, true>(ctx, p, grid, ldsb) : launch<M, N_, false>(ctx, p, grid, ldsb);
   E2_L(1, 1) E2_L(1, 2) E2_L(1, 3) E2_L(1, 4) E2_L(2, 1) E2_L(2, 2) E2_L(2, 3) E2_L(2, 4)
@@ -521,8 +516,8 @@ extern "C" int e2_conv3d_wgrad_bf16(e2_ctx* ctx, const e2_tensor5* x, const e2_t
 extern "C" int e2_conv3d_wgrad_bf16_xcl(e2_ctx* ctx, const e2_tensor5* x_shape, const void* xcl,
                                         int kg_per_plane, const e2_tensor5* dy, float* dw, int kd,
                                         int kh, int kw, int accumulate, void* ws, size_t ws_bytes) {
-  E2_REQUIRE(xcl, "conv3d_wgrad_bf16_xcl: null copy");
-  return wgrad_bf16(ctx, x_shape, xcl, kg_per_plane, dy, dw, kd, kh, kw, accumulate, ws, ws_bytes);
+  return wgrad_bf16(ctx, x_shape, xcl, kg_per_plane, dy, dw, kd, kh, kw, accumulate, ws, ws_bytes, nullptr,
+                    nullptr, true);
 }
 
 /* geometry of the ready-made operands of e2_conv3d_wgrad_bf16_ex */

@@ -1,21 +1,32 @@
 """The tiling strings of the conv GEMM launches and the keys of the tuning table, read and
-written in ONE place (host side; the library has its own parser behind ``e2_set_tiling``).
+written in ONE place on the host side.  The library reads a string in one place too,
+``e2_set_tiling`` (csrc/conv_host.hpp), and keeps the parsed list; both sides state the grammar in
+the same words (include/e2hip.h, e2_set_tiling):
 
-A tiling string is a comma-separated list of integers.  ``kind == 'igemm'`` (forward and data
-gradient):
-  "MT,NT,CC,SK"               the 16x16x4 kernel                       family '16x16x4'
-  "4,MG,NT,CC,SK,WM,WN,G"     the 4x4x1 kernel                         family '4x4x1'
-  "1,MT,NT" / "1,MT,NT,KC,0"  the pointwise (1x1x1) GEMM               family 'pointwise'
-  "32,MB,NB"                  bf16 operands in memory                  family 'memory'
-``kind == 'wgrad'`` (weight gradient):
-  "32,MB,NB,R,S"              bf16 operands in memory                  family 'memory'
-  "MT,NT,WK,BP,PS"            every other form; WK >= 100: XCD-grouped family 'wgrad'
+A tiling string is a comma-separated list of at most 8 integers (an optional '-' and decimal
+digits each, within 32 bits), nothing else -- no blanks, no '+', no trailing comma -- of at most
+63 characters.  With n integers v0, v1, ...: ``kind == 'igemm'`` (forward and data gradient):
+  n == 4                "MT,NT,CC,SK"               the 16x16x4 kernel             family '16x16x4'
+  n == 8, v0 == 4       "4,MG,NT,CC,SK,WM,WN,G"     the 4x4x1 kernel               family '4x4x1'
+  n == 3 or 5, v0 == 1  "1,MT,NT" / "1,MT,NT,KC,0"  the pointwise (1x1x1) GEMM     family 'pointwise'
+  n >= 3, v0 == 32      "32,MB,NB"                  bf16 operands in memory        family 'memory'
+``kind == 'wgrad'`` (weight gradient), n == 5:
+  v0 == 32              "32,MB,NB,R,S"              bf16 operands in memory        family 'memory'
+  otherwise             "MT,NT,WK,BP,PS"            WK >= 100: XCD-grouped         family 'wgrad'
+The rows are tried in this order.  "32,2,2,1" is therefore a 16x16x4 string here and to the
+library's packed launches, while e2_conv3d_*_bf16 -- which asks only for the last 'igemm' row --
+reads the tile (2, 2) out of it: the one string that two launchers take for their own.
+``e2_set_tiling`` also takes any 5 integers for 'igemm'; a packed launch then refuses those that
+do not start with 1.
 
 A table key is "<kind>[_bf16]|<sig>", or "side|<sig>" for the per-problem side-stream flag of a
 weight gradient; <sig> is the launch's signature, integers joined by commas.
 
 This module imports nothing from the package: it works without the shared library."""
+import re
 from collections import namedtuple
+
+_LIST = re.compile(r"-?[0-9]+(,-?[0-9]+){0,7}")
 
 
 class Tiling(namedtuple('Tiling', 'kind family v')):
@@ -34,11 +45,10 @@ class Tiling(namedtuple('Tiling', 'kind family v')):
 
 def parse(kind, s):
     """the Tiling of a string, or None for an empty, malformed or unknown one"""
-    if not s:
+    if not s or len(s) > 63 or not _LIST.fullmatch(s):
         return None
-    try:
-        v = tuple(int(t) for t in s.split(","))
-    except ValueError:
+    v = tuple(int(t) for t in s.split(","))
+    if any(abs(q) >= 2 ** 31 for q in v):
         return None
     fam = None
     if kind == 'igemm':

@@ -72,6 +72,17 @@ int  e2_set_mfma_dtype(e2_ctx* ctx, int dtype);
 int  e2_get_mfma_dtype(const e2_ctx* ctx);
 /* Tiling of the conv GEMM launches (no reference counterpart; stands where Theano's
  * per-op algorithm choice `dnn_conv3d(..., algo=...)` stood, computations.py:30,391).
+ * A tiling string is a comma-separated list of at most 8 integers (an optional '-' and decimal
+ * digits each, within 32 bits), nothing else -- no blanks, no '+', no trailing comma -- of at most
+ * 63 characters.  It is parsed HERE, once (csrc/conv_host.hpp); anything else is an error of this
+ * call.  With n integers v0, v1, ... this call accepts, for kind E2_TILING_IGEMM: n == 4, n == 5,
+ * n == 3 with v0 == 1 or 32, n == 8 with v0 == 4; for kind E2_TILING_WGRAD: n == 5.  The
+ * launches then read the list: a packed forward / dgrad / UpConv launch runs n == 4 (16x16x4),
+ * n == 3 or 5 with v0 == 1 (pointwise), n == 8 with v0 == 4 (4x4x1) and refuses every other list;
+ * e2_conv3d_{fwd,dgrad}_bf16* honour n >= 3 with v0 == 32 (so "32,2,2,1" is a 16x16x4 tiling to
+ * the former and the tile (2, 2) to the latter); e2_conv3d_wgrad* take n == 5 as "MT,NT,WK,BP,PS";
+ * e2_conv3d_wgrad_bf16* honour n == 5 with v0 == 32.  elektronn2_amd/tiling.py states the same
+ * grammar for the host side.
  * kind E2_TILING_IGEMM: cfg = "MT,NT,CC,SK" for the packed forward / dgrad / UpConv
  * launches (16x16x4 MFMA kernel: 16*MT output channels x 64*NT positions per work-group,
  * CC input channels per LDS chunk, SK-way split of K), or cfg = "4,MG,NT,CC,SK,WM,WN,G"
