@@ -120,16 +120,25 @@ void e2i_pack_dims(int cout, int cin, int* ciP, int* coP);
 
 int e2i_upconv_dpre_s2d(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* yout, int pz,
                         int py, int px, int act, float* s2d, float* dbias);
+// the weight gradient: e2i_wgrad_conv decodes the tiling into its route (conv_host.hpp) and runs the
+// LDS-staged kernel itself or hands the route to the launcher of its family
 int e2i_wgrad_conv(e2_ctx*, const WgradArgs& a);
-// conv_wgrad_direct.hip: dy operand straight from global memory (needs dy_padded)
-int e2i_wgrad_direct(e2_ctx*, const WgradArgs& a, int MT, int NT, int BP, int PS, int WK, int xcd = 0);
-int e2i_wgrad_direct_lpad(const WgradArgs& a, int BP);
-// conv_pw_wgrad.hip: 1x1x1 / UpConv weight gradient as a GEMM with K-contiguous operands
-int e2i_pw_wgrad(e2_ctx*, const WgradArgs& a, int MT, int NT, int S);
-// (even = B >= 1: S work-groups with even position ranges in B bands, wgrad_even.hpp)
-int e2i_pw_wgrad_ks(e2_ctx*, const WgradArgs& a, int MT, int NT, int S, int even);
-int e2i_wgrad_ks(e2_ctx*, const WgradArgs& a, int MT, int NT, int S, int even);     // the same for kernels with taps
+int e2i_wgrad_direct(e2_ctx*, const WgradArgs& a, const E2WgradRoute& r);   // conv_wgrad_direct.hip (needs dy_padded)
 size_t e2i_wgrad_direct_buf_floats(const WgradArgs& a, int NT, int BP, int WK);
+// conv_pw_wgrad.hip: the GEMMs with K-contiguous operands (1x1x1 / UpConv; with taps)
+int e2i_pw_wgrad(e2_ctx*, const WgradArgs& a, const E2WgradRoute& r);
+int e2i_pw_wgrad_ks(e2_ctx*, const WgradArgs& a, const E2WgradRoute& r);
+int e2i_wgrad_ks(e2_ctx*, const WgradArgs& a, const E2WgradRoute& r);
+
+// raise a kernel's dynamic-LDS limit once (*done: the flag of the launcher's template instance;
+// one device per process: plan.py get_ctx)
+static inline int e2i_raise_lds(const void* kernel, int bytes, bool* done) {
+  if (*done) return 0;
+  hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) { e2_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return 1; }
+  *done = true;
+  return 0;
+}
 
 // fill helpers (view_ops.hip, arena_ops.hip)
 int e2i_fill_view(e2_ctx*, const e2_tensor5* v, float value);

@@ -170,6 +170,97 @@ static inline WgradArgs wgrad_args(const e2_tensor5& x, const e2_tensor5& dy, fl
   return a;
 }
 
+// ---- the route of a weight-gradient launch --------------------------------------------------
+// The five integers "MT,NT,WK,BP,PS" of a weight-gradient tiling -- a forced string or the cost
+// model's choice (choose_wcfg returns integers for both) -- are decoded HERE, once per launch;
+// e2i_wgrad_conv switches on the family, the launchers read the named fields.  Tried in this
+// order (the same words: tiling.py wgrad_route):
+//   WK == 7                          the K-contiguous 1x1x1 GEMM (BP ignored)           pw_wgrad
+//   WK == 8                          ... one tile per work-group, waves split positions pw_wgrad_ks
+//   WK == 9                          ... for kernels with taps                          wgrad_ks
+//       (8 / 9 with BP >= 1: the "even" form, PS work-groups over BP bands)
+//   dy padded, WK in {1, 14, 101, 114}, BP in {128, 256}
+//                                    the direct kernel; WK % 100 == 14: the waves split
+//                                    the quads; WK >= 100: XCD-grouped block order      wgrad_direct
+//   otherwise WK == 14 or WK >= 100  refused
+//   otherwise BP not 64 or 128       refused
+//   otherwise WK in {0, 1}, or WK == 4 with NT == 1 (the waves split K)
+//                                    the LDS-staged kernel                              wgrad_lds
+//   otherwise                        refused
+// A refused route keeps the family of the LDS-staged kernel: that is the name e2_last_launch has
+// for it, noted before the refusal is raised.
+enum E2WgradFamily { E2_WG_LDS, E2_WG_DIRECT, E2_WG_PW, E2_WG_PW_KS, E2_WG_KS };
+struct E2WgradRoute {
+  int family = E2_WG_LDS;
+  int MT = 0, NT = 0;
+  int BP = 0;                   // LDS / DIRECT: positions per tile (else 0)
+  bool wave_split = false;      // LDS: WK == 4;  DIRECT: WK % 100 == 14
+  bool xcd = false;             // DIRECT: WK >= 100
+  int splits = 0;               // PS: position splits (even form: the number of work-groups)
+  int bands = 0, groups = 0;    // PW_KS / KS, even form: BP bands, PS work-groups (else 0)
+  const char* refuse = nullptr; // non-null: no kernel runs these integers, and why
+};
+static inline E2WgradRoute e2_wgrad_route(const int v[5], bool dy_padded) {
+  E2WgradRoute r;
+  const int WK = v[2], BP = v[3];
+  r.MT = v[0]; r.NT = v[1]; r.splits = v[4];
+  if (WK == 7) { r.family = E2_WG_PW; return r; }
+  if (WK == 8 || WK == 9) {
+    r.family = WK == 8 ? E2_WG_PW_KS : E2_WG_KS;
+    if (BP >= 1) { r.bands = BP; r.groups = v[4]; }
+    return r;
+  }
+  r.BP = BP;
+  if (dy_padded && (WK == 1 || WK == 14 || WK == 101 || WK == 114) && (BP == 128 || BP == 256)) {
+    r.family = E2_WG_DIRECT; r.wave_split = WK % 100 == 14; r.xcd = WK >= 100;
+    return r;
+  }
+  if (WK == 14 || WK >= 100) r.refuse = "wgrad: WK=14/101/114 need the padded-gradient entry point and BP 128/256";
+  else if (BP != 64 && BP != 128) r.refuse = "wgrad: BP must be 64 or 128";
+  else if (!(WK == 0 || WK == 1 || (WK == 4 && r.NT == 1))) r.refuse = "wgrad: WK=4 needs NT=1";
+  else r.wave_split = WK == 4;
+  return r;
+}
+static inline const char* e2_wgrad_family_name(const E2WgradRoute& r, bool bf16) {
+  switch (r.family) {
+    case E2_WG_PW: return "pw_wgrad";
+    case E2_WG_PW_KS: return "pw_wgrad_ks";
+    case E2_WG_KS: return "wgrad_ks";
+    case E2_WG_DIRECT: return bf16 ? "wgrad_direct_bf16r" : "wgrad_direct";
+  }
+  return "wgrad_lds";
+}
+
+// ---- what the K-contiguous GEMMs (WK 7 / 8 / 9) can run ---------------------------------------
+// The clause that refuses, or nullptr.  choose_wcfg asks (a forced 7 / 8 / 9 that gets a clause
+// takes the cost model's choice: "fallback"), and the launchers ask again through E2_REQUIRE.  The
+// clauses only the launchers have -- a forced string that meets one is an error -- stand there.
+// WK 7 and 8: a 1x1x1 kernel on dense channel planes, f32 mode
+static inline const char* e2_pw_wgrad_limit(const WgradArgs& a, bool bf16, int /*input_slack*/) {
+  if (!(a.kd == 1 && a.kh == 1 && a.kw == 1)) return "pointwise wgrad: the kernel is not 1x1x1";
+  if (!(a.xsY == a.Wo && a.xsZ == (int64_t)a.Ho * a.Wo && a.dsY == a.Wo && a.dsZ == (int64_t)a.Ho * a.Wo))
+    return "pointwise wgrad: x and dy need dense channel planes (row stride = W, plane stride = H * W)";
+  if (bf16) return "pointwise wgrad: an f32 kernel, not offered in bf16 mode";
+  return nullptr;
+}
+// WK 9: taps; the padded gradient at the input's row pitch with >= 31 zeros behind a plane; f32
+// mode; 128 readable bytes behind x; 32-bit byte offsets inside a sample
+static inline const char* e2_wgrad_ks_limit(const WgradArgs& a, bool bf16, int input_slack) {
+  const int64_t Din = a.Do + a.kd - 1, Hin = a.Ho + a.kh - 1;
+  const int64_t K = (int64_t)(a.Ho - 1) * a.dsY + a.Wo;       // memory span of a gradient plane
+  if (!(a.kd * a.kh * a.kw > 1 && a.upR <= 1)) return "wgrad (position-split GEMM): a conv kernel with taps";
+  if (!a.dy_padded) return "wgrad (position-split GEMM): dy must be the interior of its zero-padded buffer";
+  if (a.dsY != a.xsY) return "wgrad (position-split GEMM): dy rows at the input's pitch";
+  if ((a.kh - 1) * a.xsY + (a.kw - 1) < 31) return "wgrad (position-split GEMM): the kernel's rows leave fewer than 31 zeros behind a plane";
+  if (bf16) return "wgrad (position-split GEMM): an f32 kernel, not offered in bf16 mode";
+  if (!(a.xsZ >= Hin * a.xsY && a.xsC >= Din * a.xsZ)) return "wgrad (position-split GEMM): x planes / channels overlap";
+  if (!(((int64_t)a.Cout * a.dsC + (int64_t)a.Do * a.dsZ + K) * 4 + 256 < ((int64_t)1 << 32) &&
+        ((int64_t)a.Cin * a.xsC + Din * a.xsZ) * 4 + 256 < ((int64_t)1 << 32) && a.dsC >= 0 && a.xsC >= 0))
+    return "wgrad (position-split GEMM): sample too large for 32-bit byte offsets";
+  if (input_slack < 128) return "wgrad (position-split GEMM): needs e2_set_input_slack(ctx, >= 128)";
+  return nullptr;
+}
+
 // views the call sites cut or make up before they call a builder
 static inline e2_tensor5 e2_interior(const e2_tensor5& t, int pd, int ph, int pw) {   // of a padded buffer
   e2_tensor5 v = t;

@@ -538,13 +538,8 @@ __global__ __launch_bounds__(256) void pw_wgrad_ev_kernel(PgP p, WgEven ev) {
 template <int MT, int NT, bool TAPS>
 int launch_ev(e2_ctx* ctx, const PgP& p, const WgEven& ev) {
   const int lds = 4 * 16 * MT * (16 * NT + 4) * (int)sizeof(float);
-  static bool raised = false;                        // (one device per process: plan.py get_ctx)
-  if (!raised) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_wgrad_ev_kernel<MT, NT, TAPS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) { e2_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return 1; }
-    raised = true;
-  }
+  static bool raised = false;
+  if (int rc = e2i_raise_lds(reinterpret_cast<const void*>(&pw_wgrad_ev_kernel<MT, NT, TAPS>), lds, &raised)) return rc;
   PgP ps = p;
 #ifdef E2_DEBUG_ENV
   // debug build: do the work-groups that flush twice (or more) set the kernel's duration?
@@ -596,16 +591,11 @@ static int even_split(const PgP& p, long G, int B, WgEven* ev) {
   return 0;
 }
 
-template <int MT, int NT, bool TAPS = false>
+template <int MT, int NT, bool TAPS>
 int launch_ks(e2_ctx* ctx, const PgP& p, long grid) {
   const int lds = 4 * 16 * MT * (16 * NT + 4) * (int)sizeof(float);
-  static bool raised = false;                        // (one device per process: plan.py get_ctx)
-  if (!raised) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_wgrad_ks_kernel<MT, NT, TAPS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) { e2_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return 1; }
-    raised = true;
-  }
+  static bool raised = false;
+  if (int rc = e2i_raise_lds(reinterpret_cast<const void*>(&pw_wgrad_ks_kernel<MT, NT, TAPS>), lds, &raised)) return rc;
 #ifdef E2_DEBUG_ENV
   // in-kernel timeline (debug build): mean s_memtime ticks between the stamps over the work-groups
   PgP ps = p;
@@ -649,88 +639,102 @@ int launch(e2_ctx* ctx, const PgP& p, long grid) {
   return 0;
 }
 
-}  // namespace
-
-int e2i_pw_wgrad(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S) {
-  E2_REQUIRE(a.kd == 1 && a.kh == 1 && a.kw == 1, "pointwise wgrad: kernel %dx%dx%d is not 1x1x1", a.kd, a.kh, a.kw);
-  E2_REQUIRE(a.xsY == a.Wo && a.xsZ == (int64_t)a.Ho * a.Wo && a.dsY == a.Wo && a.dsZ == (int64_t)a.Ho * a.Wo,
-             "pointwise wgrad: x and dy need dense channel planes (row stride = W, plane stride = H * W)");
-  E2_REQUIRE(!ctx->mfma_bf16, "pointwise wgrad: an f32 kernel, not offered in bf16 mode");
+// ---- host side of the three forms ---------------------------------------------------------------
+// what all three fill alike: the GEMM dy[M][k] x x[Ncol][k] over samples of K positions, as a
+// 1x1x1 problem without UpConv rows (the form with taps overwrites the tap members)
+PgP pg_base(const WgradArgs& a, int Ncol, long K) {
   PgP p;
   p.a = a.dy; p.b = a.x; p.c = a.dw;
   p.asN = a.dsN; p.asC = a.dsC; p.bsN = a.xsN; p.bsC = a.xsC;
-  p.N = a.N; p.M = a.Cout; p.Ncol = a.Cin;
+  p.N = a.N; p.M = a.Cout; p.Ncol = Ncol;
+  p.K = (int)K;
+  p.R = 1; p.rem = 0; p.stamps = nullptr;
+  p.T = 1; p.kh = p.kw = 1; p.flip = 0; p.planes = 1; p.asZ = p.bsZ = p.bsY = 0;
+  return p;
+}
+
+// The position split of forms 8 and 9 (p.nMT, p.nNT and p.stepsPerSample are set): `units` whole
+// 32-position units over r.splits work-groups per tile, whole rounds of the four waves each, the
+// grid padded to the XCD-grouped order; or, even form, r.groups work-groups with even ranges in
+// r.bands bands.  Then the zero fill: the next thing the caller does is launch.
+struct KsSplit { long grid; bool even; WgEven ev; };
+int ks_split(e2_ctx* ctx, const WgradArgs& a, const E2WgradRoute& r, long units, const char* who, PgP& p, KsSplit* k) {
+  E2_REQUIRE(units < (1L << 29), "%s: too many positions", who);
+  p.steps = (int)units;
+  const int S = (int)std::max<long>(1, std::min<long>(r.splits, std::max<long>(1, (units + 3) / 4)));
+  p.per = (int)std::max<long>(1, (units + S - 1) / S);
+  p.per = (p.per + 3) & ~3;                          // whole rounds of the four waves
+  p.S = (int)std::max<long>(1, (units + p.per - 1) / p.per);
+  k->grid = (long)p.nMT * p.nNT * p.S;
+  k->grid = (k->grid + 7) & ~7L;                     // XCD-grouped order (the pad returns at once)
+  E2_REQUIRE(k->grid < (1L << 31), "%s: grid too large", who);
+  k->even = r.bands >= 1;
+  k->ev = WgEven{};
+  if (k->even)
+    if (int rc = even_split(p, r.groups, r.bands, &k->ev)) return rc;
+  if (!a.accumulate)
+    if (int rc = e2i_fill_flat(ctx, a.dw, (size_t)a.Cout * p.Ncol, 0.f)) return rc;
+  return 0;
+}
+template <int MT, int NT, bool TAPS>
+int launch_split(e2_ctx* ctx, const PgP& p, const KsSplit& k) {
+  return k.even ? launch_ev<MT, NT, TAPS>(ctx, p, k.ev) : launch_ks<MT, NT, TAPS>(ctx, p, k.grid);
+}
+
+}  // namespace
+
+// "MT,NT,7,0,S": every wave its own output blocks, S position splits (pw_wgrad_kernel)
+int e2i_pw_wgrad(e2_ctx* ctx, const WgradArgs& a, const E2WgradRoute& r) {
+  const char* limit = e2_pw_wgrad_limit(a, ctx->mfma_bf16 != 0, ctx->input_slack);
+  E2_REQUIRE(!limit, "%s", limit);
   const long K = (long)a.Do * a.Ho * a.Wo;
   E2_REQUIRE(K < (1L << 30), "pointwise wgrad: sample too large");
-  p.K = (int)K;
+  PgP p = pg_base(a, a.Cin, K);
   p.R = a.upR > 1 ? a.upR : 1;
   E2_REQUIRE(a.Cout % p.R == 0, "pointwise wgrad: %d rows for %d sub-positions", a.Cout, p.R);
-  p.nMT = e2_cdiv(a.Cout, 32 * MT);
-  p.nNT = e2_cdiv(a.Cin, 32 * NT);
-  p.rem = 0; p.stamps = nullptr;
-  p.T = 1; p.kh = p.kw = 1; p.flip = 0; p.planes = 1; p.asZ = p.bsZ = p.bsY = 0;
+  p.nMT = e2_cdiv(a.Cout, 32 * r.MT);
+  p.nNT = e2_cdiv(a.Cin, 32 * r.NT);
   p.stepsPerSample = (int)((K + 15) / 16);
   const long steps = (long)a.N * p.stepsPerSample;
   E2_REQUIRE(steps < (1L << 30), "pointwise wgrad: too many positions");
   p.steps = (int)steps;
-  S = (int)std::max<long>(1, std::min<long>(S, steps));
+  const int S = (int)std::max<long>(1, std::min<long>(r.splits, steps));
   p.per = (int)((steps + S - 1) / S);
   p.S = (int)((steps + p.per - 1) / p.per);
   const long grid = (long)p.nMT * p.nNT * p.S;
   E2_REQUIRE(grid < (1L << 31), "pointwise wgrad: grid too large");
   if (!a.accumulate)
     if (int rc = e2i_fill_flat(ctx, a.dw, (size_t)a.Cout * a.Cin, 0.f)) return rc;
-#define E2_L(M, N_) if (MT == M && NT == N_) return launch<M, N_>(ctx, p, grid);
+#define E2_L(M, N_) if (r.MT == M && r.NT == N_) return launch<M, N_>(ctx, p, grid);
   E2_L(2, 2) E2_L(4, 2) E2_L(2, 4) E2_L(4, 4) E2_L(4, 3) E2_L(3, 4) E2_L(7, 2) E2_L(2, 7) E2_L(7, 4) E2_L(4, 7)
 #undef E2_L
-  e2_set_error("pointwise wgrad: no instance MT=%d NT=%d", MT, NT);
+  e2_set_error("pointwise wgrad: no instance MT=%d NT=%d", r.MT, r.NT);
   return 2;
 }
 
 // "MT,NT,8,0,S": the waves of a work-group split the positions (pw_wgrad_ks_kernel);
-// "MT,NT,8,B,G" (even = B >= 1): G work-groups with even position ranges in B bands (pw_wgrad_ev_kernel)
-int e2i_pw_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S, int even) {
-  E2_REQUIRE(a.kd == 1 && a.kh == 1 && a.kw == 1, "pointwise wgrad: kernel %dx%dx%d is not 1x1x1", a.kd, a.kh, a.kw);
-  E2_REQUIRE(a.xsY == a.Wo && a.xsZ == (int64_t)a.Ho * a.Wo && a.dsY == a.Wo && a.dsZ == (int64_t)a.Ho * a.Wo,
-             "pointwise wgrad: x and dy need dense channel planes (row stride = W, plane stride = H * W)");
-  E2_REQUIRE(!ctx->mfma_bf16, "pointwise wgrad: an f32 kernel, not offered in bf16 mode");
-  PgP p;
-  p.a = a.dy; p.b = a.x; p.c = a.dw;
-  p.asN = a.dsN; p.asC = a.dsC; p.bsN = a.xsN; p.bsC = a.xsC;
-  p.N = a.N; p.M = a.Cout; p.Ncol = a.Cin;
+// "MT,NT,8,B,G", B >= 1: G work-groups with even position ranges in B bands (pw_wgrad_ev_kernel)
+int e2i_pw_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, const E2WgradRoute& r) {
+  const char* limit = e2_pw_wgrad_limit(a, ctx->mfma_bf16 != 0, ctx->input_slack);
+  E2_REQUIRE(!limit, "%s", limit);
   const long K = (long)a.Do * a.Ho * a.Wo;
   E2_REQUIRE(K >= 4 && K < (1L << 30), "pointwise wgrad: sample of %ld positions", K);
   // 32-bit element offsets of a row inside its sample (+ the 32 positions of a unit)
   E2_REQUIRE(((long)a.Cout * a.dsC + K) * 4 < (1L << 32) && ((long)a.Cin * a.xsC + K) * 4 < (1L << 32) && a.dsC >= 0 && a.xsC >= 0,
              "pointwise wgrad: sample too large for 32-bit byte offsets");
-  p.K = (int)K;
+  PgP p = pg_base(a, a.Cin, K);
   p.R = a.upR > 1 ? a.upR : 1;
   E2_REQUIRE(a.Cout % p.R == 0, "pointwise wgrad: %d rows for %d sub-positions", a.Cout, p.R);
-  p.nMT = e2_cdiv(a.Cout, 16 * MT);
-  p.nNT = e2_cdiv(a.Cin, 16 * NT);
+  p.nMT = e2_cdiv(a.Cout, 16 * r.MT);
+  p.nNT = e2_cdiv(a.Cin, 16 * r.NT);
   p.stepsPerSample = (int)(K / 32);                  // (here: WHOLE 32-position units)
-  p.rem = (int)(K % 32); p.stamps = nullptr;
-  p.T = 1; p.kh = p.kw = 1; p.flip = 0; p.planes = 1; p.asZ = p.bsZ = p.bsY = 0;
-  const long units = (long)a.N * p.stepsPerSample;
-  E2_REQUIRE(units < (1L << 29), "pointwise wgrad: too many positions");
-  p.steps = (int)units;
-  const long S0 = S;                                 // (even: the number of work-groups)
-  S = (int)std::max<long>(1, std::min<long>(S, std::max<long>(1, (units + 3) / 4)));
-  p.per = (int)std::max<long>(1, (units + S - 1) / S);
-  p.per = (p.per + 3) & ~3;                          // whole rounds of the four waves
-  p.S = (int)std::max<long>(1, (units + p.per - 1) / p.per);
-  long grid = (long)p.nMT * p.nNT * p.S;
-  grid = (grid + 7) & ~7L;                           // XCD-grouped order (the pad returns at once)
-  E2_REQUIRE(grid < (1L << 31), "pointwise wgrad: grid too large");
-  WgEven ev{};
-  if (even > 0)
-    if (int rc = even_split(p, S0, even, &ev)) return rc;
-  if (!a.accumulate)
-    if (int rc = e2i_fill_flat(ctx, a.dw, (size_t)a.Cout * a.Cin, 0.f)) return rc;
-#define E2_L(M, N_) if (MT == M && NT == N_) return even > 0 ? launch_ev<M, N_, false>(ctx, p, ev) : launch_ks<M, N_>(ctx, p, grid);
+  p.rem = (int)(K % 32);
+  KsSplit k;
+  if (int rc = ks_split(ctx, a, r, (long)a.N * p.stepsPerSample, "pointwise wgrad", p, &k)) return rc;
+#define E2_L(M, N_) if (r.MT == M && r.NT == N_) return launch_split<M, N_, false>(ctx, p, k);
   E2_L(13, 2) E2_L(7, 2) E2_L(7, 4) E2_L(4, 4) E2_L(10, 2)
 #undef E2_L
-  e2_set_error("pointwise wgrad (position-split waves): no instance MT=%d NT=%d", MT, NT);
+  e2_set_error("pointwise wgrad (position-split waves): no instance MT=%d NT=%d", r.MT, r.NT);
   return 2;
 }
 
@@ -743,34 +747,21 @@ int e2i_pw_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S, int 
 // Units are whole: one that runs past the end of its plane multiplies dy's zero border ((kh - 1)
 // rows >= 31 positions: required) with whatever x holds there -- the next plane / channel / sample,
 // or up to 124 bytes behind the tensor, which the caller vouches for (e2_set_input_slack).
-int e2i_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S, int even) {
+int e2i_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, const E2WgradRoute& r) {
+  const char* limit = e2_wgrad_ks_limit(a, ctx->mfma_bf16 != 0, ctx->input_slack);
+  E2_REQUIRE(!limit, "%s", limit);
   const int T = a.kd * a.kh * a.kw;
-  E2_REQUIRE(T > 1 && a.upR <= 1, "wgrad (position-split GEMM): a conv kernel with taps");
-  E2_REQUIRE(a.dy_padded, "wgrad (position-split GEMM): dy must be the interior of its zero-padded buffer");
-  E2_REQUIRE(a.dsY == a.xsY, "wgrad (position-split GEMM): dy rows at the input's pitch (%ld vs %ld)", (long)a.dsY, (long)a.xsY);
-  E2_REQUIRE((a.kh - 1) * a.xsY + (a.kw - 1) >= 31, "wgrad (position-split GEMM): %d x %d kernel rows of %ld leave fewer than 31 zeros behind a plane",
-             a.kh, a.kw, (long)a.xsY);
-  E2_REQUIRE(!ctx->mfma_bf16, "wgrad (position-split GEMM): an f32 kernel, not offered in bf16 mode");
-  const int Din = a.Do + a.kd - 1, Hin = a.Ho + a.kh - 1;
-  E2_REQUIRE(a.xsZ >= (int64_t)Hin * a.xsY && a.xsC >= (int64_t)Din * a.xsZ, "wgrad (position-split GEMM): x planes / channels overlap");
-  PgP p;
-  p.a = a.dy; p.b = a.x; p.c = a.dw;
-  p.asN = a.dsN; p.asC = a.dsC; p.bsN = a.xsN; p.bsC = a.xsC;
-  p.N = a.N; p.M = a.Cout; p.Ncol = a.Cin * T;
   const long K = (long)(a.Ho - 1) * a.dsY + a.Wo;             // memory span of a gradient plane
   E2_REQUIRE(K >= 4 && K < (1L << 28), "wgrad (position-split GEMM): plane of %ld positions", K);
-  E2_REQUIRE(((long)a.Cout * a.dsC + (long)a.Do * a.dsZ + K) * 4 + 256 < (1L << 32) &&
-                 ((long)a.Cin * a.xsC + (long)Din * a.xsZ) * 4 + 256 < (1L << 32) && a.dsC >= 0 && a.xsC >= 0,
-             "wgrad (position-split GEMM): sample too large for 32-bit byte offsets");
-  p.K = (int)K; p.R = 1; p.rem = 0; p.stamps = nullptr;
+  PgP p = pg_base(a, a.Cin * T, K);
   p.T = T; p.kh = a.kh; p.kw = a.kw; p.flip = a.flip; p.planes = a.Do;
   p.asZ = a.dsZ; p.bsZ = a.xsZ; p.bsY = a.xsY;
-  E2_REQUIRE(ctx->input_slack >= 128, "wgrad (position-split GEMM): needs e2_set_input_slack(ctx, >= 128)");
 #ifdef E2_DEBUG_ENV
   // debug build (make DEBUG_ENV=1): CHECK the caller's promise -- the 32 floats behind the last
   // element of x must be finite (they meet the gradient's zero border: 0 x Inf / NaN = NaN in dW
   // where the reference produces none).  Synchronises: never during capture.
   if (!ctx->capturing) {
+    const int Din = a.Do + a.kd - 1, Hin = a.Ho + a.kh - 1;
     const float* end = a.x + (int64_t)(a.N - 1) * a.xsN + (int64_t)(a.Cin - 1) * a.xsC +
                        (int64_t)(Din - 1) * a.xsZ + (int64_t)(Hin - 1) * a.xsY + (a.Wo + a.kw - 1);
     float h[32];
@@ -781,28 +772,14 @@ int e2i_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int S, int eve
                  "values behind x, but float %d behind its last element is %g", i, (double)h[i]);
   }
 #endif
-  p.nMT = e2_cdiv(a.Cout, 16 * MT);
-  p.nNT = e2_cdiv(p.Ncol, 16 * NT);
+  p.nMT = e2_cdiv(a.Cout, 16 * r.MT);
+  p.nNT = e2_cdiv(p.Ncol, 16 * r.NT);
   p.stepsPerSample = (int)((K + 31) / 32);                    // (whole units of a PLANE)
-  const long units = (long)a.N * a.Do * p.stepsPerSample;
-  E2_REQUIRE(units < (1L << 29), "wgrad (position-split GEMM): too many positions");
-  p.steps = (int)units;
-  const long S0 = S;                                          // (even: the number of work-groups)
-  S = (int)std::max<long>(1, std::min<long>(S, std::max<long>(1, (units + 3) / 4)));
-  p.per = (int)std::max<long>(1, (units + S - 1) / S);
-  p.per = (p.per + 3) & ~3;
-  p.S = (int)std::max<long>(1, (units + p.per - 1) / p.per);
-  long grid = (long)p.nMT * p.nNT * p.S;
-  grid = (grid + 7) & ~7L;
-  E2_REQUIRE(grid < (1L << 31), "wgrad (position-split GEMM): grid too large");
-  WgEven ev{};
-  if (even > 0)
-    if (int rc = even_split(p, S0, even, &ev)) return rc;
-  if (!a.accumulate)
-    if (int rc = e2i_fill_flat(ctx, a.dw, (size_t)a.Cout * p.Ncol, 0.f)) return rc;
-#define E2_L(M, N_) if (MT == M && NT == N_) return even > 0 ? launch_ev<M, N_, true>(ctx, p, ev) : launch_ks<M, N_, true>(ctx, p, grid);
+  KsSplit k;
+  if (int rc = ks_split(ctx, a, r, (long)a.N * a.Do * p.stepsPerSample, "wgrad (position-split GEMM)", p, &k)) return rc;
+#define E2_L(M, N_) if (r.MT == M && r.NT == N_) return launch_split<M, N_, true>(ctx, p, k);
   E2_L(13, 2) E2_L(7, 2) E2_L(7, 4) E2_L(4, 4) E2_L(10, 2) E2_L(5, 4) E2_L(3, 4) E2_L(2, 4) E2_L(8, 2) E2_L(8, 4) E2_L(6, 4)
 #undef E2_L
-  e2_set_error("wgrad (position-split GEMM): no instance MT=%d NT=%d", MT, NT);
+  e2_set_error("wgrad (position-split GEMM): no instance MT=%d NT=%d", r.MT, r.NT);
   return 2;
 }

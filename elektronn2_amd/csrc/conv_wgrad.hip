@@ -26,36 +26,9 @@
 // Inner loop: "quads" of 4 k-steps.  All LDS reads of quad q+1 are issued (asm,
 // invisible to hipcc's waitcnt pass) before the MFMAs of quad q; one
 // s_waitcnt lgkmcnt(0) after the MFMAs.  Two register sets ping-pong.
-#include "stream_common.hpp"
+#include "wgrad_common.hpp"
 #include <stdlib.h>
-#include <algorithm>
 #include <utility>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_vp;
-typedef const __attribute__((address_space(1))) void* gbl_vp;
-
-__device__ __forceinline__ void w_glds4(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds((gbl_vp)g, (lds_vp)l, 4, 0, 0);
-}
-__device__ __forceinline__ void w_glds16(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds((gbl_vp)g, (lds_vp)l, 16, 0, 0);
-}
-template <int OFF>
-__device__ __forceinline__ float w_lds_ld(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-__device__ __forceinline__ i32x4 w_lds_ld128(unsigned addr) {
-  i32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
-__device__ __forceinline__ unsigned w_lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(lds_vp)p;
-}
 
 struct WgradP {
   const float* x;
@@ -78,18 +51,6 @@ struct WgradP {
   int bf16;               // operands rounded to bf16 into the matrix core (padded-gradient entry only)
   FastDiv divWo;
 };
-
-__device__ __forceinline__ f32x4 w_lds_ld128f(unsigned addr, int off_dummy = 0) {
-  f32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ f32x4 w_lds_ld128o(unsigned addr) {
-  f32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
 
 // one quad = 16 positions = 4 k-steps.  K is permuted so that lane quarter qd
 // owns positions 16q + 4qd + j (j = k-step): its A operands of the 4 steps are 4
@@ -118,7 +79,7 @@ struct QuadRegs {
   }
   template <int... I>
   __device__ __forceinline__ void load_a(unsigned addr, std::integer_sequence<int, I...>) {
-    ((a[I] = w_lds_ld128o<I * 16 * DLPAD * 4>(addr)), ...);
+    ((a[I] = wg_lds_ld128_off<I * 16 * DLPAD * 4>(addr)), ...);
   }
   __device__ __forceinline__ void load(unsigned addrA, unsigned addrT, unsigned xbase,
                                        const int (&lanebase)[NT], const i32x4& cur_io) {
@@ -127,23 +88,14 @@ struct QuadRegs {
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int nb = 0; nb < NT; ++nb)
-        b[j][nb] = w_lds_ld<0>(xbase + 4u * (unsigned)(lanebase[nb] + cur_io[j]));
-    io = w_lds_ld128(addrT);
+        b[j][nb] = wg_lds_ld_off<0>(xbase + 4u * (unsigned)(lanebase[nb] + cur_io[j]));
+    io = wg_lds_ld128(addrT);
   }
 };
 
 // bf16 operand form (e2_set_mfma_dtype): the four k-steps a lane holds of a quad are
 // exactly the k = 4*qd + j layout of v_mfma_f32_16x16x16_bf16 -- operands rounded to
-// bf16 (nearest even) by plain casts (NOT inline asm: the compiler must see the VALU
-// write to place the wait states in front of the MFMA), f32 sums.
-typedef short w_s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 w_bf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ w_s16x4 w_pack_bf16(float a, float b, float c, float d) {
-  union { w_bf16x4 h; w_s16x4 v; } r;
-  r.h = (w_bf16x4){(__bf16)a, (__bf16)b, (__bf16)c, (__bf16)d};
-  return r.v;
-}
-
+// bf16 (wg_pack_bf16), f32 sums.
 template <int MT, int NT, int BP, int WK, bool BF>
 __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradP p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -227,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradP p) {
         float* dst = dyl + co * DLPAD + 64 * j;
         const int cg = min(m0 + co, p.Cout - 1);
         // invalid positions must contribute 0
-        w_glds4(valid ? src + (long)cg * p.dsC : p.zeros, dst);
+        wg_glds4(valid ? src + (long)cg * p.dsC : p.zeros, dst);
       }
     }
     // input spans, 16 B per lane; the tensor's very last row goes by dwords
@@ -239,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradP p) {
       const int ci = ciA + cs;
       const float* src = xb + (long)ci * p.xsC + (long)dz * p.xsZ;
       float* dst = xl + slot * Lpad;
-      for (int j = 0; j < nJ; ++j) w_glds4(src + min(64 * j + lane, L - 1), dst + 64 * j);
+      for (int j = 0; j < nJ; ++j) wg_glds4(src + min(64 * j + lane, L - 1), dst + 64 * j);
     }
   };
 
@@ -257,19 +209,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradP p) {
     if (tt + 1 < te && !(p.dbg & 1)) stage(tt + 1, cur ^ 1);
     if (p.dbg & 2) continue;
     const float* dyl = smem + cur * p.bufFloats;
-    const unsigned xbase = w_lds_addr(dyl + DYF + TBF);
+    const unsigned xbase = wg_lds_addr(dyl + DYF + TBF);
     // A: row (mb*16 + l15), columns 16*quad + 4*qd .. +3 ; table: natural order
-    unsigned addrA = w_lds_addr(dyl + l15 * DLPAD + 4 * qd) + 64u * (unsigned)wk;
-    unsigned addrT = w_lds_addr(dyl + DYF + 4 * qd) + 64u * (unsigned)wk;
+    unsigned addrA = wg_lds_addr(dyl + l15 * DLPAD + 4 * qd) + 64u * (unsigned)wk;
+    unsigned addrT = wg_lds_addr(dyl + DYF + 4 * qd) + 64u * (unsigned)wk;
 
     QuadRegs<MT, NT, DLPAD> g0, g1;
 #define E2_MFMA(G)                                                       \
     if constexpr (BF) {                                                  \
-      w_s16x4 bb_[NT];                                                   \
+      s16x4 bb_[NT];                                                   \
       _Pragma("unroll") for (int nb = 0; nb < NT; ++nb)                  \
-        bb_[nb] = w_pack_bf16(G.b[0][nb], G.b[1][nb], G.b[2][nb], G.b[3][nb]); \
+        bb_[nb] = wg_pack_bf16(G.b[0][nb], G.b[1][nb], G.b[2][nb], G.b[3][nb]); \
       _Pragma("unroll") for (int mb = 0; mb < MT; ++mb) {                \
-        const w_s16x4 aa_ = w_pack_bf16(G.a[mb][0], G.a[mb][1], G.a[mb][2], G.a[mb][3]); \
+        const s16x4 aa_ = wg_pack_bf16(G.a[mb][0], G.a[mb][1], G.a[mb][2], G.a[mb][3]); \
         _Pragma("unroll") for (int nb = 0; nb < NT; ++nb)                \
           acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(aa_, bb_[nb], acc[mb][nb], 0, 0, 0); \
       }                                                                  \
@@ -283,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradP p) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   \
     __builtin_amdgcn_sched_barrier(0);
     // first quad of this wave: its offsets, then its operands
-    i32x4 io0 = w_lds_ld128(addrT);
+    i32x4 io0 = wg_lds_ld128(addrT);
     E2_WAIT()
     asm volatile("" : "+v"(io0));
     addrT += 64u * WK;
@@ -348,13 +300,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradP p) {
 template <int MT, int NT, int BP, int WK, bool BF>
 static int launch_w2(e2_ctx* ctx, const WgradP& p, int grid, size_t lds) {
   static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&wgrad_kernel<MT, NT, BP, WK, BF>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { e2_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return 1; }
-    attr_done = true;
-  }
+  if (int rc = e2i_raise_lds(reinterpret_cast<const void*>(&wgrad_kernel<MT, NT, BP, WK, BF>), 160 * 1024, &attr_done))
+    return rc;
   hipLaunchKernelGGL((wgrad_kernel<MT, NT, BP, WK, BF>), dim3(grid), dim3(256), lds, ctx->stream, p);
   E2_CHECK_HIP(hipGetLastError());
   return 0;
@@ -367,11 +314,9 @@ static int launch_w(e2_ctx* ctx, const WgradP& p, int grid, size_t lds) {
   return launch_w2<MT, NT, BP, WK, false>(ctx, p, grid, lds);
 }
 
-static const int kWMTs[] = {1, 2, 3, 4, 5, 7};
-
+// the instances: NT 1 / 2 / 4 with WK 1, NT 1 with WK 4 (the route refuses other NT there)
 template <int MT>
-static int dispatch_w2(e2_ctx* ctx, const WgradP& p, int NT, int BP, int WK, int grid,
-                       size_t lds) {
+static int dispatch_w(e2_ctx* ctx, const WgradP& p, int NT, int BP, int WK, int grid, size_t lds) {
   if (WK == 4) {
     if (BP == 64) return launch_w<MT, 1, 64, 4>(ctx, p, grid, lds);
     return launch_w<MT, 1, 128, 4>(ctx, p, grid, lds);
@@ -389,20 +334,6 @@ static int dispatch_w2(e2_ctx* ctx, const WgradP& p, int NT, int BP, int WK, int
   return 2;
 }
 
-static int dispatch_w(e2_ctx* ctx, const WgradP& p, int MT, int NT, int BP, int WK, int grid,
-                      size_t lds) {
-  switch (MT) {
-    case 1: return dispatch_w2<1>(ctx, p, NT, BP, WK, grid, lds);
-    case 2: return dispatch_w2<2>(ctx, p, NT, BP, WK, grid, lds);
-    case 3: return dispatch_w2<3>(ctx, p, NT, BP, WK, grid, lds);
-    case 4: return dispatch_w2<4>(ctx, p, NT, BP, WK, grid, lds);
-    case 5: return dispatch_w2<5>(ctx, p, NT, BP, WK, grid, lds);
-    case 7: return dispatch_w2<7>(ctx, p, NT, BP, WK, grid, lds);
-  }
-  e2_set_error("wgrad: no instance MT=%d", MT);
-  return 2;
-}
-
 // x-span row stride: whole 64-float (dword) DMA pieces, == 2 (mod 4) so rows of
 // consecutive channels fall on different banks
 static int w_lpad(int Lmax) {
@@ -412,16 +343,10 @@ static int w_lmax(const WgradArgs& a, int BP) {
   const int rows = (BP + a.Wo - 2) / a.Wo;      // rows crossed by BP consecutive positions
   return (BP - 1) + rows * ((int)a.xsY - a.Wo) + (a.kh - 1) * (int)a.xsY + a.kw;
 }
-static int w_maxspans(const WgradArgs& a, int BNn) {
-  const int T = a.kd * a.kh * a.kw;
-  int cis = (BNn - 1) / T + 2;
-  if (cis > a.Cin) cis = a.Cin;
-  return cis * a.kd;
-}
 static size_t w_buf_floats(const WgradArgs& a, int MT, int BNn, int BP) {
   const size_t dyf = (((size_t)16 * MT * (BP + 4) + 3) / 4) * 4;
   // + slack: the quad pipeline prefetches one quad past the end of the tile
-  return dyf + (BP + 128) + (size_t)w_maxspans(a, BNn) * w_lpad(w_lmax(a, BP)) + 64;
+  return dyf + (BP + 128) + (size_t)wg_maxspans(a, BNn) * w_lpad(w_lmax(a, BP)) + 64;
 }
 
 struct WCfg { int MT, NT, WK, BP, PS; };
@@ -444,33 +369,24 @@ static WCfg choose_wcfg(const e2_ctx* ctx, const WgradArgs& a, int* ok, int* src
     *src = E2_SRC_FALLBACK;           // ... unless one of the returns below honours the string
     if (e2_wgrad_candidate(t)) {
       const WCfg f{t.v[0], t.v[1], t.v[2], t.v[3], t.v[4]};
-      // "MT,NT,7,0,S" names the K-contiguous 1x1x1 GEMM (conv_pw_wgrad.hip), which takes dense
-      // channel planes and f32 mode only.  The tuning keys hold the row pitch, not the plane
-      // pitch: a view that keeps the rows but not the planes (a crop along the second spatial
-      // axis of the parent) matches a shipped entry it cannot run -- such a call takes the
-      // cost model's choice instead of failing.
-      const bool pw_ok = a.kd == 1 && a.kh == 1 && a.kw == 1 && a.xsY == a.Wo &&
-                         a.xsZ == (int64_t)a.Ho * a.Wo && a.dsY == a.Wo &&
-                         a.dsZ == (int64_t)a.Ho * a.Wo && !ctx->mfma_bf16;
-      // "MT,NT,9,0,S": the same GEMM for kernels with taps; needs the padded gradient at the
-      // input's row pitch and a zero border of >= 31 positions behind a plane
-      // (and 32-bit byte offsets inside a sample: a larger problem takes the cost model's choice)
-      const long spanK = (long)(a.Ho - 1) * a.dsY + a.Wo;
-      const bool ks_fits = ((long)a.Cout * a.dsC + (long)a.Do * a.dsZ + spanK) * 4 + 256 < (1L << 32) &&
-                           ((long)a.Cin * a.xsC + (long)(a.Do + a.kd - 1) * a.xsZ) * 4 + 256 < (1L << 32) &&
-                           a.dsC >= 0 && a.xsC >= 0 && a.xsZ >= (int64_t)(a.Ho + a.kh - 1) * a.xsY &&
-                           a.xsC >= (int64_t)(a.Do + a.kd - 1) * a.xsZ;
-      const bool ks_ok = a.dy_padded && a.kd * a.kh * a.kw > 1 && a.upR <= 1 && a.dsY == a.xsY &&
-                         (a.kh - 1) * a.xsY + (a.kw - 1) >= 31 && !ctx->mfma_bf16 &&
-                         ctx->input_slack >= 128 && ks_fits;
-      if (f.WK == 9) { if (ks_ok) { *ok = 1; *src = E2_SRC_FORCED; return f; } }
-      else if ((f.WK != 7 && f.WK != 8) || pw_ok) { *ok = 1; *src = E2_SRC_FORCED; return f; }
+      // "MT,NT,7,0,S" / "MT,NT,8,..." name the K-contiguous 1x1x1 GEMM (conv_pw_wgrad.hip), which
+      // takes dense channel planes and f32 mode only.  The tuning keys hold the row pitch, not the
+      // plane pitch: a view that keeps the rows but not the planes (a crop along the second spatial
+      // axis of the parent) matches a shipped entry it cannot run -- such a call takes the cost
+      // model's choice instead of failing.  "MT,NT,9,...": the same GEMM for kernels
+      // with taps; a problem outside its limits takes the cost model's choice too.  Every other
+      // string is returned as it is: what no kernel runs is refused by its route or its launcher.
+      // (The limits: conv_host.hpp; the launchers hold clauses these two do not)
+      const char* limit = f.WK == 9 ? e2_wgrad_ks_limit(a, ctx->mfma_bf16, ctx->input_slack)
+                          : (f.WK == 7 || f.WK == 8) ? e2_pw_wgrad_limit(a, ctx->mfma_bf16, ctx->input_slack)
+                          : nullptr;
+      if (limit == nullptr) { *ok = 1; *src = E2_SRC_FORCED; return f; }
     }
   }
   if (a.dy_padded && nblocks > 2) {
     // direct kernel (conv_wgrad_direct.hip): no dy staging; tiles of 128/256 span positions
     const long S = (long)(a.Ho - 1) * a.dsY + a.Wo;
-    for (int MT : kWMTs) {
+    for (int MT : kWgMTs) {
       if (MT > mblocks && MT != 1) continue;
       const int nMT = e2_cdiv(mblocks, MT);
       for (int NT = 1; NT <= 4; NT *= 2) {
@@ -503,7 +419,10 @@ static WCfg choose_wcfg(const e2_ctx* ctx, const WgradArgs& a, int* ok, int* src
     }
     if (best.MT) { *ok = 1; return best; }
   }
-  for (int MT : kWMTs) {
+  // The LDS-staged kernel, priced as such.  For a padded call (nblocks <= 2, or no direct tiling
+  // fits) a choice {MT, NT, 1, 128, PS} of this loop has the integers of the direct kernel's
+  // route: the DIRECT kernel runs it, and e2_last_launch says so.  Known and kept.
+  for (int MT : kWgMTs) {
     if (MT > mblocks && MT != 1) continue;
     const int nMT = e2_cdiv(mblocks, MT);
     for (int v = 0; v < 4; ++v) {
@@ -529,7 +448,7 @@ static WCfg choose_wcfg(const e2_ctx* ctx, const WgradArgs& a, int* ok, int* src
           PS = std::min(PS, tiles);
           const int per = (int)((tiles + PS - 1) / PS);
           const double mfma = (BP / 4.0 / WK) * MT * NT * 32.0;              // per tile
-          const double bytes = 4.0 * (16.0 * MT * BP + (double)w_maxspans(a, BNn) * w_lmax(a, BP));
+          const double bytes = 4.0 * (16.0 * MT * BP + (double)wg_maxspans(a, BNn) * w_lmax(a, BP));
           const double issue = (BP / 4.0 / WK) * (MT + 2.0 * NT + 1) * 5.0;
           double tile = std::max(mfma, issue) * perCU * 1.08 + 400.0;
           tile = std::max(tile, bytes / 20.0 * perCU);
@@ -553,65 +472,32 @@ int e2i_wgrad_conv(e2_ctx* ctx, const WgradArgs& a) {
              "wgrad: empty problem");
   E2_REQUIRE(a.xsY < (1 << 20), "wgrad: input row stride too large");
   int ok = 0, src = E2_SRC_MODEL;
-  WCfg c = choose_wcfg(ctx, a, &ok, &src);
+  const WCfg c = choose_wcfg(ctx, a, &ok, &src);
   E2_REQUIRE(ok, "wgrad: no tiling fits LDS (Cin=%d Cout=%d k=%dx%dx%d)", a.Cin, a.Cout,
              a.kd, a.kh, a.kw);
-  {
-    // e2_last_launch: the kernel family this call is about to run, its tiling, and whether a
-    // forced string was honoured ("fallback": a 7 / 8 / 9 form the problem's layout cannot run)
-    const bool direct = a.dy_padded && (c.WK == 1 || c.WK == 14 || c.WK == 101 || c.WK == 114) &&
-                        (c.BP == 128 || c.BP == 256);
-    const char* fam = c.WK == 7 ? "pw_wgrad" : c.WK == 8 ? "pw_wgrad_ks" : c.WK == 9 ? "wgrad_ks"
-                      : direct ? (ctx->mfma_bf16 ? "wgrad_direct_bf16r" : "wgrad_direct")
-                      : "wgrad_lds";
-    e2_note_launch(ctx, fam, src, "%d,%d,%d,%d,%d", c.MT, c.NT, c.WK, c.BP, c.PS);
+  // the one reading of the five integers (conv_host.hpp)
+  const int v[5] = {c.MT, c.NT, c.WK, c.BP, c.PS};
+  const E2WgradRoute r = e2_wgrad_route(v, a.dy_padded != 0);
+  // e2_last_launch: the kernel family this call is about to run, its tiling, and whether a
+  // forced string was honoured ("fallback": a 7 / 8 / 9 form the problem's layout cannot run)
+  e2_note_launch(ctx, e2_wgrad_family_name(r, ctx->mfma_bf16 != 0), src, "%d,%d,%d,%d,%d", c.MT, c.NT, c.WK, c.BP, c.PS);
+  E2_REQUIRE(!r.refuse, "%s", r.refuse);
+  switch (r.family) {
+    case E2_WG_PW: return e2i_pw_wgrad(ctx, a, r);
+    case E2_WG_PW_KS: return e2i_pw_wgrad_ks(ctx, a, r);
+    case E2_WG_KS: return e2i_wgrad_ks(ctx, a, r);
+    case E2_WG_DIRECT: return e2i_wgrad_direct(ctx, a, r);
   }
-  // WK field: 1 = direct kernel when dy is padded (BP 128/256), else the LDS-staged
-  // kernel; 14 = direct kernel, waves split the quads of a tile (NT 2/4);
-  // 0 = LDS-staged kernel forced; 4 = LDS-staged kernel, waves split K
-  // WK 101 / 114: the direct kernel with the XCD-grouped block order (nMT * PS % 8 == 0)
-  // WK 7 ("MT,NT,7,0,S"): 1x1x1 kernels -- the GEMM with K-contiguous operands (conv_pw_wgrad.hip)
-  // WK 8 ("MT,NT,8,0,S"): the same GEMM, one 16 MT x 16 NT tile per work-group whose four waves split the positions
-  if (c.WK == 7) return e2i_pw_wgrad(ctx, a, c.MT, c.NT, c.PS);
-  if (c.WK == 8) return e2i_pw_wgrad_ks(ctx, a, c.MT, c.NT, c.PS, c.BP);
-  // "MT,NT,8,B,G" / "MT,NT,9,B,G", B >= 1: the same tiles, G work-groups with EVEN position
-  // ranges in B bands (wgrad_even.hpp)
-  // WK 9 ("MT,NT,9,0,S"): that GEMM for kernels WITH taps -- every (input channel, tap) column of dW is
-  // a K-contiguous row of x at the tap's shift (needs the padded gradient at the input's row pitch)
-  if (c.WK == 9) return e2i_wgrad_ks(ctx, a, c.MT, c.NT, c.PS, c.BP);
-  if (a.dy_padded && (c.WK == 1 || c.WK == 14 || c.WK == 101 || c.WK == 114) && (c.BP == 128 || c.BP == 256))
-    return e2i_wgrad_direct(ctx, a, c.MT, c.NT, c.BP, c.PS, (c.WK % 100) == 14 ? 4 : 1, c.WK >= 100);
-  E2_REQUIRE(c.WK != 14 && c.WK < 100, "wgrad: WK=14/101/114 need the padded-gradient entry point and BP 128/256");
-  if (c.WK == 0) c.WK = 1;
-  E2_REQUIRE(c.BP == 64 || c.BP == 128, "wgrad: BP must be 64 or 128");
-  E2_REQUIRE(c.WK == 1 || (c.WK == 4 && c.NT == 1), "wgrad: WK=4 needs NT=1");
+  // the LDS-staged kernel
+  const int WK = r.wave_split ? 4 : 1, WN = 4 / WK;
+  const int BNn = 16 * r.NT * WN;
   WgradP p;
-  p.x = a.x; p.dy = a.dy; p.dw = a.dw;
+  if (int rc = wg_fill(p, a, r.MT, r.NT * WN, a.Ho * a.Wo, r.BP, r.splits)) return rc;
   p.zeros = ctx->zeros;
-  p.Cin = a.Cin; p.Cout = a.Cout; p.kd = a.kd; p.kh = a.kh; p.kw = a.kw;
-  p.THW = a.kh * a.kw; p.T = a.kd * p.THW;
-  p.Do = a.Do; p.Ho = a.Ho; p.Wo = a.Wo; p.Q = a.Ho * a.Wo;
-  p.xsN = a.xsN; p.xsC = a.xsC; p.xsZ = a.xsZ; p.xsY = a.xsY;
-  p.dsN = a.dsN; p.dsC = a.dsC; p.dsZ = a.dsZ; p.dsY = a.dsY;
-  p.flip = a.flip;
-  p.upR = a.upR > 1 ? a.upR : 1;
-  const long NTOT = (long)a.Cin * p.T;
-  E2_REQUIRE(NTOT < (1L << 30), "wgrad: Cin*T too large");
-  p.NTOT = (int)NTOT;
-  const int WN = 4 / c.WK;
-  const int BNn = 16 * c.NT * WN;
-  p.Lpad = w_lpad(w_lmax(a, c.BP));
-  p.maxSpans = w_maxspans(a, BNn);
-  p.nMT = e2_cdiv(e2_cdiv(a.Cout, 16), c.MT);
-  p.nNT = e2_cdiv(e2_cdiv(p.NTOT, 16), c.NT * WN);
-  p.nPT = e2_cdiv(p.Q, c.BP);
-  p.tilesTotal = a.N * a.Do * p.nPT;
-  p.nPS = std::max(1, std::min(c.PS, p.tilesTotal));
-  p.bufFloats = (int)w_buf_floats(a, c.MT, BNn, c.BP);
-  p.Din = a.Do + a.kd - 1;
-  p.N = a.N;
+  p.Q = a.Ho * a.Wo;
+  p.Lpad = w_lpad(w_lmax(a, r.BP));
+  p.bufFloats = (int)w_buf_floats(a, r.MT, BNn, r.BP);
   p.divWo = mk_div((unsigned)a.Wo);
-  p.dbg = e2_dbg_env_int("E2_WGRAD_DBG");
   p.bf16 = (ctx->mfma_bf16 && a.dy_padded) ? 1 : 0;
   size_t lds = 2 * (size_t)p.bufFloats * 4;
   lds += (size_t)e2_dbg_env_int("E2_WGRAD_LDSPAD");
@@ -622,6 +508,10 @@ int e2i_wgrad_conv(e2_ctx* ctx, const WgradArgs& a) {
     if (int rc = e2i_fill_flat(ctx, a.dw, (size_t)a.Cout * p.NTOT, 0.f)) return rc;
   if (e2_dbg_env("E2_VERBOSE"))
     fprintf(stderr, "[e2] wgrad%s Cin=%d Cout=%d k=%d,%d,%d out=%d,%d,%d MT=%d NT=%d WK=%d BP=%d PS=%d grid=%ld lds=%zu\n",
-            p.bf16 ? "(bf16)" : "", a.Cin, a.Cout, a.kd, a.kh, a.kw, a.Do, a.Ho, a.Wo, c.MT, c.NT, c.WK, c.BP, p.nPS, grid, lds);
-  return dispatch_w(ctx, p, c.MT, c.NT, c.BP, c.WK, (int)grid, lds);
+            p.bf16 ? "(bf16)" : "", a.Cin, a.Cout, a.kd, a.kh, a.kw, a.Do, a.Ho, a.Wo, r.MT, r.NT, WK, r.BP, p.nPS, grid, lds);
+  const int rc = wg_with_mt(r.MT, [&](auto mt) {
+    return dispatch_w<decltype(mt)::value>(ctx, p, r.NT, r.BP, WK, (int)grid, lds);
+  });
+  E2_REQUIRE(rc >= 0, "wgrad: no instance MT=%d", r.MT);
+  return rc;
 }

@@ -21,44 +21,12 @@
 // Positions past the end of a plane's span (the last one or two quads of a plane) are
 // masked out of A with v_cndmask after the load; the loads themselves may run up to
 // 31 floats past the span, hence the 128 B of slack the entry point asks for.
-#include "stream_common.hpp"
+#include "wgrad_common.hpp"
 #include <stdlib.h>
-#include <algorithm>
 #include <vector>
 #include <utility>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_vp;
-typedef const __attribute__((address_space(1))) void* gbl_vp;
-
 namespace {
-
-__device__ __forceinline__ void d_glds4(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds((gbl_vp)g, (lds_vp)l, 4, 0, 0);
-}
-__device__ __forceinline__ void d_glds16(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds((gbl_vp)g, (lds_vp)l, 16, 0, 0);
-}
-__device__ __forceinline__ float d_lds_ld(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
-__device__ __forceinline__ i32x4 d_lds_ld128(unsigned addr) {
-  i32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
-__device__ __forceinline__ f32x4 d_gl_ld128(const float* sbase, unsigned voff) {
-  f32x4 v;
-  asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(voff), "s"(sbase));
-  return v;
-}
-__device__ __forceinline__ unsigned d_lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(lds_vp)p;
-}
 
 struct WdP {
   const float* x;
@@ -99,7 +67,7 @@ struct DQuad {
   }
   __device__ __forceinline__ void load_a(const float* abase, const unsigned (&voff)[MT]) {
 #pragma unroll
-    for (int mb = 0; mb < MT; ++mb) a[mb] = d_gl_ld128(abase, voff[mb]);
+    for (int mb = 0; mb < MT; ++mb) a[mb] = wg_gl_ld128(abase, voff[mb]);
   }
   __device__ __forceinline__ void load_b(unsigned addrT, unsigned xbase, const int (&lanebase)[NT],
                                          const i32x4& cur_io) {
@@ -107,8 +75,8 @@ struct DQuad {
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int nb = 0; nb < NT; ++nb)
-        b[j][nb] = d_lds_ld(xbase + 4u * (unsigned)(lanebase[nb] + cur_io[j]));
-    io = d_lds_ld128(addrT);
+        b[j][nb] = wg_lds_ld(xbase + 4u * (unsigned)(lanebase[nb] + cur_io[j]));
+    io = wg_lds_ld128(addrT);
   }
   // zero the k-steps whose span position lies past `lim` (relative to the quad's lane)
   __device__ __forceinline__ void mask(int lim) {
@@ -134,13 +102,13 @@ template <int MT, int NT, int R>
 __device__ __forceinline__ void dquad_read(DQuad<MT, NT>& g, const DAddr<MT, NT>& ad,
                                            const i32x4& cur_io) {
   if constexpr (R < MT) {
-    g.a[R] = d_gl_ld128(ad.abase, ad.voff[R]);
+    g.a[R] = wg_gl_ld128(ad.abase, ad.voff[R]);
   } else if constexpr (R == MT) {
-    g.io = d_lds_ld128(ad.addrT);
+    g.io = wg_lds_ld128(ad.addrT);
   } else {
     constexpr int rb = R - MT - 1;
     constexpr int j = rb / NT, nb = rb % NT;
-    g.b[j][nb] = d_lds_ld(ad.xbase + 4u * (unsigned)(ad.lanebase[nb] + cur_io[j]));
+    g.b[j][nb] = wg_lds_ld(ad.xbase + 4u * (unsigned)(ad.lanebase[nb] + cur_io[j]));
   }
 }
 template <int MT, int NT, int R0, int R1>
@@ -176,15 +144,6 @@ __device__ __forceinline__ void dquad_steps(const DQuad<MT, NT>& cur, DQuad<MT, 
 // the way into the matrix core, sums stay f32: ONE MFMA per (row block, column block)
 // and quad instead of four.  The MFMA phase is then far shorter than a round trip to
 // L2, so all loads of the next quad are issued first.
-// (plain conversions -> v_cvt_pk_bf16_f32; not inline asm, so that the compiler places the
-// wait states between the VALU write and the MFMA that reads it)
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ s16x4 d_pack_bf16(float a, float b, float c, float d) {
-  union { bf16x4 h; s16x4 v; } r;
-  r.h = (bf16x4){(__bf16)a, (__bf16)b, (__bf16)c, (__bf16)d};   // two v_cvt_pk_bf16_f32
-  return r.v;
-}
 template <int MT, int NT, bool PF>
 __device__ __forceinline__ void dquad_steps_bf(const DQuad<MT, NT>& cur, DQuad<MT, NT>& nxt,
                                                f32x4 (&acc)[MT][NT], const DAddr<MT, NT>& ad,
@@ -194,10 +153,10 @@ __device__ __forceinline__ void dquad_steps_bf(const DQuad<MT, NT>& cur, DQuad<M
   s16x4 bb[NT];
 #pragma unroll
   for (int nb = 0; nb < NT; ++nb)
-    bb[nb] = d_pack_bf16(cur.b[0][nb], cur.b[1][nb], cur.b[2][nb], cur.b[3][nb]);
+    bb[nb] = wg_pack_bf16(cur.b[0][nb], cur.b[1][nb], cur.b[2][nb], cur.b[3][nb]);
 #pragma unroll
   for (int mb = 0; mb < MT; ++mb) {
-    const s16x4 aa = d_pack_bf16(cur.a[mb][0], cur.a[mb][1], cur.a[mb][2], cur.a[mb][3]);
+    const s16x4 aa = wg_pack_bf16(cur.a[mb][0], cur.a[mb][1], cur.a[mb][2], cur.a[mb][3]);
 #pragma unroll
     for (int nb = 0; nb < NT; ++nb)
       acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(aa, bb[nb], acc[mb][nb], 0, 0, 0);
@@ -312,11 +271,11 @@ __global__ __launch_bounds__(512, 1) void wgrad_direct_kernel(WdP p) {
         if (!tail_row) {
           for (int j = 0; j < nJ16; ++j) {
             const int u = 256 * j + 4 * lane;
-            if (u < L) d_glds16(src + u, dst + 256 * j);
+            if (u < L) wg_glds16(src + u, dst + 256 * j);
           }
         } else {
           for (int j = 0; j < nJ; ++j)
-            if (64 * j + lane < L) d_glds4(src + 64 * j + lane, dst + 64 * j);
+            if (64 * j + lane < L) wg_glds4(src + 64 * j + lane, dst + 64 * j);
         }
       }
     };
@@ -411,10 +370,10 @@ __global__ __launch_bounds__(512, 1) void wgrad_direct_kernel(WdP p) {
       }
       __syncthreads();                                 // tile tt landed; the other buffer is free
       const float* bufp = smem + ((tt - tb) & 1) * p.bufFloats;
-      ad.xbase = d_lds_addr(bufp + TBF);
-      ad.addrT = d_lds_addr(bufp + 4 * qd) + 64u * (unsigned)wk;
-      i32x4 io0 = d_lds_ld128(ad.addrT);
-      i32x4 io1 = d_lds_ld128(ad.addrT + 64u * WK);
+      ad.xbase = wg_lds_addr(bufp + TBF);
+      ad.addrT = wg_lds_addr(bufp + 4 * qd) + 64u * (unsigned)wk;
+      i32x4 io0 = wg_lds_ld128(ad.addrT);
+      i32x4 io1 = wg_lds_ld128(ad.addrT + 64u * WK);
       ad.addrT += 128u * WK;                           // offsets of quad 2
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
@@ -462,9 +421,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_direct_kernel(WdP p) {
     tile_geom(tb);
     g0.load_a(ad.abase, ad.voff);                     // dy does not depend on the LDS contents
     __syncthreads();                                  // the producers' table + spans landed
-    ad.xbase = d_lds_addr(smem + TBF);
-    ad.addrT = d_lds_addr(smem + 4 * qd) + 64u * (unsigned)wk;
-    i32x4 io0 = d_lds_ld128(ad.addrT);
+    ad.xbase = wg_lds_addr(smem + TBF);
+    ad.addrT = wg_lds_addr(smem + 4 * qd) + 64u * (unsigned)wk;
+    i32x4 io0 = wg_lds_ld128(ad.addrT);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("" : "+v"(io0));
@@ -504,9 +463,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_direct_kernel(WdP p) {
       tile_geom(tt + 1);
       __syncthreads();                                // tile tt+1 landed; nobody reads tile tt's buffer any more
       const float* bufp = smem + ((tt + 1 - tb) & 1) * p.bufFloats;
-      ad.xbase = d_lds_addr(bufp + TBF);
-      ad.addrT = d_lds_addr(bufp + 4 * qd) + 64u * (unsigned)wk;
-      i32x4 io0 = d_lds_ld128(ad.addrT);
+      ad.xbase = wg_lds_addr(bufp + TBF);
+      ad.addrT = wg_lds_addr(bufp + 4 * qd) + 64u * (unsigned)wk;
+      i32x4 io0 = wg_lds_ld128(ad.addrT);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("" : "+v"(io0));
@@ -567,13 +526,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_direct_kernel(WdP p) {
 template <int MT, int NT, int BP, int WK, bool BF>
 static int launch_d2(e2_ctx* ctx, const WdP& p, int grid, size_t lds) {
   static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&wgrad_direct_kernel<MT, NT, BP, WK, BF>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { e2_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return 1; }
-    attr_done = true;
-  }
+  if (int rc = e2i_raise_lds(reinterpret_cast<const void*>(&wgrad_direct_kernel<MT, NT, BP, WK, BF>), 160 * 1024, &attr_done))
+    return rc;
   hipLaunchKernelGGL((wgrad_direct_kernel<MT, NT, BP, WK, BF>), dim3(grid), dim3(512), lds, ctx->stream, p);
   E2_CHECK_HIP(hipGetLastError());
   return 0;
@@ -616,22 +570,16 @@ static int dispatch_d2(e2_ctx* ctx, const WdP& p, int NT, int BP, int WK, int gr
 
 }  // namespace
 
-// geometry helpers shared with the host-side tiling choice (conv_wgrad.hip)
-int e2i_wgrad_direct_lpad(const WgradArgs& a, int BP) {
+// geometry helpers; the buffer size is shared with the host-side tiling choice (conv_wgrad.hip)
+static int d_lpad(const WgradArgs& a, int BP) {
   const int rows = (BP + (int)a.dsY - 2) / (int)a.dsY;      // rows crossed by BP span positions
   const int lmax = rows * (int)a.xsY + (a.Wo - 1) + (a.kh - 1) * (int)a.xsY + a.kw;
   int lp = ((lmax + 3 + 3) / 4) * 4;                        // + the straddling DMA lane
   if ((lp & 31) == 0) lp += 4;
   return lp;
 }
-static int d_maxspans(const WgradArgs& a, int BNn) {
-  const int T = a.kd * a.kh * a.kw;
-  int cis = (BNn - 1) / T + 2;
-  if (cis > a.Cin) cis = a.Cin;
-  return cis * a.kd;
-}
 size_t e2i_wgrad_direct_buf_floats(const WgradArgs& a, int NT, int BP, int WK) {
-  return (size_t)(BP + 256) + (size_t)d_maxspans(a, 16 * NT * (4 / WK)) * e2i_wgrad_direct_lpad(a, BP) + 64;
+  return (size_t)(BP + 256) + (size_t)wg_maxspans(a, 16 * NT * (4 / WK)) * d_lpad(a, BP) + 64;
 }
 
 // debug (E2_WGRAD_STAMPS): the work-groups' timeline stamps, read back and printed after a sync;
@@ -658,38 +606,20 @@ static int wgrad_stamps_report(e2_ctx* ctx, long grid, int per, double ideal) {
   return 0;
 }
 
-int e2i_wgrad_direct(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int BP, int PS, int WK, int xcd) {
-  E2_REQUIRE(BP == 128 || BP == 256, "wgrad(direct): BP must be 128 or 256");
-  E2_REQUIRE(WK == 1 || (WK == 4 && (NT == 2 || NT == 4)), "wgrad(direct): WK=4 needs NT 2 or 4");
+int e2i_wgrad_direct(e2_ctx* ctx, const WgradArgs& a, const E2WgradRoute& r) {
+  const int MT = r.MT, NT = r.NT, BP = r.BP;                // (BP 128 or 256: the route)
+  const int WK = r.wave_split ? 4 : 1;
+  E2_REQUIRE(WK == 1 || NT == 2 || NT == 4, "wgrad(direct): WK=4 needs NT 2 or 4");
   E2_REQUIRE(a.xsY < (1 << 20) && a.dsY < (1 << 20), "wgrad: row stride too large");
   E2_REQUIRE((long)a.Cout * a.dsC < (1L << 29), "wgrad(direct): gradient sample too large");
   WdP p;
-  p.x = a.x; p.dy = a.dy; p.dw = a.dw;
-  p.Cin = a.Cin; p.Cout = a.Cout; p.kd = a.kd; p.kh = a.kh; p.kw = a.kw;
-  p.THW = a.kh * a.kw; p.T = a.kd * p.THW;
-  p.Do = a.Do; p.Ho = a.Ho; p.Wo = a.Wo;
-  p.S = (a.Ho - 1) * (int)a.dsY + a.Wo;
-  p.xsN = a.xsN; p.xsC = a.xsC; p.xsZ = a.xsZ; p.xsY = a.xsY;
-  p.dsN = a.dsN; p.dsC = a.dsC; p.dsZ = a.dsZ; p.dsY = a.dsY;
-  p.flip = a.flip;
-  p.upR = a.upR > 1 ? a.upR : 1;
-  const long NTOT = (long)a.Cin * p.T;
-  E2_REQUIRE(NTOT < (1L << 30), "wgrad: Cin*T too large");
-  p.NTOT = (int)NTOT;
-  const int BNn = 16 * NT * (4 / WK);
-  p.Lpad = e2i_wgrad_direct_lpad(a, BP);
-  p.maxSpans = d_maxspans(a, BNn);
-  p.nMT = e2_cdiv(e2_cdiv(a.Cout, 16), MT);
-  p.nNT = e2_cdiv(e2_cdiv(p.NTOT, 16), NT * (4 / WK));
-  p.nPT = e2_cdiv(p.S, BP);
-  p.tilesTotal = a.N * a.Do * p.nPT;
-  p.nPS = std::max(1, std::min(PS, p.tilesTotal));
+  const int S = (a.Ho - 1) * (int)a.dsY + a.Wo;
+  if (int rc = wg_fill(p, a, MT, NT * (4 / WK), S, BP, r.splits)) return rc;
+  p.S = S;
+  p.Lpad = d_lpad(a, BP);
   p.bufFloats = (int)e2i_wgrad_direct_buf_floats(a, NT, BP, WK);
-  p.Din = a.Do + a.kd - 1;
-  p.N = a.N;
   p.divDsY = mk_div((unsigned)a.dsY);
-  p.dbg = e2_dbg_env_int("E2_WGRAD_DBG");
-  p.xcd = xcd ? 1 : 0;
+  p.xcd = r.xcd ? 1 : 0;
   const size_t lds = 2 * (size_t)p.bufFloats * 4;
   E2_REQUIRE(lds <= 160 * 1024, "wgrad(direct): tiling needs %zu B of LDS", lds);
   const long pairs = (long)p.nMT * p.nPS * p.nNT;
@@ -707,16 +637,10 @@ int e2i_wgrad_direct(e2_ctx* ctx, const WgradArgs& a, int MT, int NT, int BP, in
   if (e2_dbg_env("E2_VERBOSE"))
     fprintf(stderr, "[e2] wgrad(direct%s) Cin=%d Cout=%d k=%d,%d,%d out=%d,%d,%d MT=%d NT=%d BP=%d WK=%d PS=%d grid=%ld lds=%zu\n",
             ctx->mfma_bf16 ? ", bf16" : "", a.Cin, a.Cout, a.kd, a.kh, a.kw, a.Do, a.Ho, a.Wo, MT, NT, BP, WK, p.nPS, grid, lds);
-  int rc = 2;
-  switch (MT) {
-    case 1: rc = dispatch_d2<1>(ctx, p, NT, BP, WK, (int)grid, lds); break;
-    case 2: rc = dispatch_d2<2>(ctx, p, NT, BP, WK, (int)grid, lds); break;
-    case 3: rc = dispatch_d2<3>(ctx, p, NT, BP, WK, (int)grid, lds); break;
-    case 4: rc = dispatch_d2<4>(ctx, p, NT, BP, WK, (int)grid, lds); break;
-    case 5: rc = dispatch_d2<5>(ctx, p, NT, BP, WK, (int)grid, lds); break;
-    case 7: rc = dispatch_d2<7>(ctx, p, NT, BP, WK, (int)grid, lds); break;
-    default: e2_set_error("wgrad(direct): no instance MT=%d", MT);
-  }
+  const int rc = wg_with_mt(MT, [&](auto mt) {
+    return dispatch_d2<decltype(mt)::value>(ctx, p, NT, BP, WK, (int)grid, lds);
+  });
+  E2_REQUIRE(rc >= 0, "wgrad(direct): no instance MT=%d", MT);
   if (rc == 0 && want_stamps) {
     const int per = (p.tilesTotal + p.nPS - 1) / p.nPS;
     return wgrad_stamps_report(ctx, grid, per, (double)per * (BP / 4 / WK) * MT * NT * 32.0);

@@ -12,7 +12,7 @@ digits each, within 32 bits), nothing else -- no blanks, no '+', no trailing com
   n >= 3, v0 == 32      "32,MB,NB"                  bf16 operands in memory        family 'memory'
 ``kind == 'wgrad'`` (weight gradient), n == 5:
   v0 == 32              "32,MB,NB,R,S"              bf16 operands in memory        family 'memory'
-  otherwise             "MT,NT,WK,BP,PS"            WK >= 100: XCD-grouped         family 'wgrad'
+  otherwise             "MT,NT,WK,BP,PS"            its kernel: wgrad_route        family 'wgrad'
 The rows are tried in this order.  "32,2,2,1" is therefore a 16x16x4 string here and to the
 library's packed launches, while e2_conv3d_*_bf16 -- which asks only for the last 'igemm' row --
 reads the tile (2, 2) out of it: the one string that two launchers take for their own.
@@ -29,18 +29,68 @@ from collections import namedtuple
 _LIST = re.compile(r"-?[0-9]+(,-?[0-9]+){0,7}")
 
 
+WgradRoute = namedtuple('WgradRoute', 'family MT NT WK BP wave_split xcd splits bands groups refuse')
+
+
 class Tiling(namedtuple('Tiling', 'kind family v')):
     """a parsed tiling string: its kind, its kernel family and its integers"""
     __slots__ = ()
 
     @property
     def WK(self):
-        return self.v[2] if self.family == 'wgrad' else None
+        return wgrad_route(self, True).WK if self.family == 'wgrad' else None
 
     @property
     def xcd_grouped(self):
-        """weight gradient: the XCD-grouped block order"""
-        return self.family == 'wgrad' and self.v[2] >= 100
+        """weight gradient: the direct kernel with the XCD-grouped block order (as the launch plan
+        calls it: through the padded-gradient entry point)"""
+        return self.family == 'wgrad' and wgrad_route(self, True).xcd
+
+
+def wgrad_route(t, dy_padded, bf16=False):
+    """The kernel a 'wgrad' tiling "MT,NT,WK,BP,PS" runs, as the library decodes it -- once per
+    launch, csrc/conv_host.hpp e2_wgrad_route; ``family`` is the name e2_last_launch reports.  Tried
+    in this order (the same words: conv_host.hpp):
+      WK == 7                          the K-contiguous 1x1x1 GEMM (BP ignored)           pw_wgrad
+      WK == 8                          ... one tile per work-group, waves split positions pw_wgrad_ks
+      WK == 9                          ... for kernels with taps                          wgrad_ks
+          (8 / 9 with BP >= 1: the "even" form, PS work-groups over BP bands)
+      dy padded, WK in {1, 14, 101, 114}, BP in {128, 256}
+                                       the direct kernel; WK % 100 == 14: the waves split
+                                       the quads; WK >= 100: XCD-grouped block order      wgrad_direct
+      otherwise WK == 14 or WK >= 100  refused
+      otherwise BP not 64 or 128       refused
+      otherwise WK in {0, 1}, or WK == 4 with NT == 1 (the waves split K)
+                                       the LDS-staged kernel                              wgrad_lds
+      otherwise                        refused
+    A refused route keeps the family of the LDS-staged kernel (``refuse``: why).  ``dy_padded``: the
+    launch comes through the padded-gradient entry point (the launch plan's always do); ``bf16``:
+    the operands are rounded to bf16, which only the direct kernel's name shows.  BP is 0 where it
+    is no tile length, bands / groups are 0 outside the even form; WK is the field as written."""
+    assert t.kind == 'wgrad' and t.family == 'wgrad', t
+    MT, NT, WK, BP, PS = t.v
+    r = dict(family='wgrad_lds', MT=MT, NT=NT, WK=WK, BP=0, wave_split=False, xcd=False, splits=PS,
+             bands=0, groups=0, refuse=None)
+    if WK == 7:
+        r.update(family='pw_wgrad')
+    elif WK in (8, 9):
+        r.update(family='pw_wgrad_ks' if WK == 8 else 'wgrad_ks')
+        if BP >= 1:
+            r.update(bands=BP, groups=PS)
+    elif dy_padded and WK in (1, 14, 101, 114) and BP in (128, 256):
+        r.update(family='wgrad_direct_bf16r' if bf16 else 'wgrad_direct', BP=BP,
+                 wave_split=WK % 100 == 14, xcd=WK >= 100)
+    else:
+        r.update(BP=BP)
+        if WK == 14 or WK >= 100:
+            r.update(refuse="WK=14/101/114 need the padded-gradient entry point and BP 128/256")
+        elif BP not in (64, 128):
+            r.update(refuse="BP must be 64 or 128")
+        elif not (WK in (0, 1) or (WK == 4 and NT == 1)):
+            r.update(refuse="WK=4 needs NT=1")
+        else:
+            r.update(wave_split=WK == 4)
+    return WgradRoute(**r)
 
 
 def parse(kind, s):

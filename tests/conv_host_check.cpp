@@ -1,7 +1,10 @@
 // Host check of csrc/conv_host.hpp (built and run by tests/test_conv_host.py with the host
 // compiler and -fsanitize=address,undefined): the tiling grammar of e2_set_tiling against a table
-// written out by hand, and the builders of the conv GEMM arguments against literal members.
+// written out by hand, the builders of the conv GEMM arguments against literal members, the route
+// of a weight-gradient tiling against a table written out by hand and against the if-chain it
+// replaced, and the limits of the K-contiguous weight-gradient GEMMs on literal problems.
 #include <stdio.h>
+#include <string.h>
 #include <string>
 #include <vector>
 #include "conv_host.hpp"
@@ -217,9 +220,233 @@ static int check_builders() {
   return 0;
 }
 
+// ---- the route of a weight-gradient tiling --------------------------------------------------
+struct RouteRow {
+  const char* s;
+  bool padded;
+  int family, MT, NT, BP;
+  bool wave_split, xcd;
+  int splits, bands, groups;
+  bool refused;
+};
+static const int L = E2_WG_LDS, D = E2_WG_DIRECT, PW = E2_WG_PW, PK = E2_WG_PW_KS, KS = E2_WG_KS;
+static const RouteRow kRoutes[] = {
+    // WK 0 / 1 / 4: the LDS-staged kernel, BP 64 / 128; WK 1 with BP 128 / 256 only where dy is not padded
+    {"1,1,0,64,2", false, L, 1, 1, 64, false, false, 2, 0, 0, false},
+    {"1,1,0,128,2", true, L, 1, 1, 128, false, false, 2, 0, 0, false},     // (0: LDS-staged, forced)
+    {"1,1,1,64,2", true, L, 1, 1, 64, false, false, 2, 0, 0, false},
+    {"1,1,1,64,2", false, L, 1, 1, 64, false, false, 2, 0, 0, false},
+    {"1,1,1,128,2", false, L, 1, 1, 128, false, false, 2, 0, 0, false},
+    {"5,4,1,128,0", false, L, 5, 4, 128, false, false, 0, 0, 0, false},
+    {"1,1,1,256,2", false, L, 1, 1, 256, false, false, 2, 0, 0, true},
+    {"1,1,4,64,2", false, L, 1, 1, 64, true, false, 2, 0, 0, false},
+    {"7,1,4,128,1", true, L, 7, 1, 128, true, false, 1, 0, 0, false},
+    {"1,2,4,64,1", false, L, 1, 2, 64, false, false, 1, 0, 0, true},
+    {"1,2,4,64,1", true, L, 1, 2, 64, false, false, 1, 0, 0, true},
+    // WK 1 / 14 / 101 / 114 on the padded gradient, BP 128 / 256: the direct kernel
+    {"1,1,1,128,2", true, D, 1, 1, 128, false, false, 2, 0, 0, false},
+    {"1,1,1,256,2", true, D, 1, 1, 256, false, false, 2, 0, 0, false},
+    {"1,2,14,128,2", true, D, 1, 2, 128, true, false, 2, 0, 0, false},
+    {"3,4,14,256,3", true, D, 3, 4, 256, true, false, 3, 0, 0, false},
+    {"7,2,101,128,8", true, D, 7, 2, 128, false, true, 8, 0, 0, false},
+    {"2,2,101,256,5", true, D, 2, 2, 256, false, true, 5, 0, 0, false},
+    {"3,2,114,128,7", true, D, 3, 2, 128, true, true, 7, 0, 0, false},
+    {"3,2,114,256,7", true, D, 3, 2, 256, true, true, 7, 0, 0, false},
+    // ... and nowhere else
+    {"1,2,14,128,2", false, L, 1, 2, 128, false, false, 2, 0, 0, true},
+    {"1,1,14,64,2", true, L, 1, 1, 64, false, false, 2, 0, 0, true},
+    {"7,2,101,128,8", false, L, 7, 2, 128, false, false, 8, 0, 0, true},
+    {"1,1,101,64,2", true, L, 1, 1, 64, false, false, 2, 0, 0, true},
+    {"3,2,114,64,7", true, L, 3, 2, 64, false, false, 7, 0, 0, true},
+    {"1,1,100,128,2", true, L, 1, 1, 128, false, false, 2, 0, 0, true},
+    {"1,1,55,128,1", true, L, 1, 1, 128, false, false, 1, 0, 0, true},
+    {"1,1,55,128,1", false, L, 1, 1, 128, false, false, 1, 0, 0, true},
+    {"1,1,-1,64,2", false, L, 1, 1, 64, false, false, 2, 0, 0, true},
+    {"1,1,1,0,2", true, L, 1, 1, 0, false, false, 2, 0, 0, true},
+    // WK 7 / 8 / 9: the K-contiguous GEMMs, whatever the entry point; BP ignored (7) or the bands
+    {"2,2,7,0,3", true, PW, 2, 2, 0, false, false, 3, 0, 0, false},
+    {"2,2,7,5,3", true, PW, 2, 2, 0, false, false, 3, 0, 0, false},
+    {"2,2,7,128,3", false, PW, 2, 2, 0, false, false, 3, 0, 0, false},
+    {"13,2,8,0,4", true, PK, 13, 2, 0, false, false, 4, 0, 0, false},
+    {"7,2,8,3,16", true, PK, 7, 2, 0, false, false, 16, 3, 16, false},
+    {"7,2,8,-3,16", false, PK, 7, 2, 0, false, false, 16, 0, 0, false},
+    {"13,2,9,0,4", true, KS, 13, 2, 0, false, false, 4, 0, 0, false},
+    {"7,2,9,3,512", true, KS, 7, 2, 0, false, false, 512, 3, 512, false},
+    {"7,2,9,128,4", true, KS, 7, 2, 0, false, false, 4, 128, 4, false},
+    {"7,2,9,1,0", false, KS, 7, 2, 0, false, false, 0, 1, 0, false},
+};
+
+static int same(const E2WgradRoute& r, const RouteRow& w, const char* s, int padded) {
+  CHECK(r.family == w.family, "'%s' padded %d: family %d", s, padded, r.family);
+  CHECK(r.MT == w.MT && r.NT == w.NT, "'%s' padded %d: tile %d x %d", s, padded, r.MT, r.NT);
+  CHECK(r.BP == w.BP, "'%s' padded %d: BP %d", s, padded, r.BP);
+  CHECK(r.wave_split == w.wave_split, "'%s' padded %d: wave_split %d", s, padded, (int)r.wave_split);
+  CHECK(r.xcd == w.xcd, "'%s' padded %d: xcd %d", s, padded, (int)r.xcd);
+  CHECK(r.splits == w.splits, "'%s' padded %d: splits %d", s, padded, r.splits);
+  CHECK(r.bands == w.bands && r.groups == w.groups, "'%s' padded %d: bands %d groups %d", s, padded, r.bands, r.groups);
+  CHECK((r.refuse != nullptr) == w.refused, "'%s' padded %d: refused %d", s, padded, (int)(r.refuse != nullptr));
+  return 0;
+}
+
+// The if-chain e2i_wgrad_conv had before the route (commit 6dbc609), kept here as the oracle: the
+// same conditions in the same order, the launcher calls and E2_REQUIREs replaced by a record of
+// which was reached with what.  `even` / S of the forms 8 and 9 read as their launchers read them
+// (even > 0: `even` bands, S work-groups).
+struct WCfg { int MT, NT, WK, BP, PS; };
+static RouteRow old_chain(WCfg c, bool dy_padded, bool mfma_bf16, const char** fam_out) {
+  {
+    const bool direct = dy_padded && (c.WK == 1 || c.WK == 14 || c.WK == 101 || c.WK == 114) &&
+                        (c.BP == 128 || c.BP == 256);
+    const char* fam = c.WK == 7 ? "pw_wgrad" : c.WK == 8 ? "pw_wgrad_ks" : c.WK == 9 ? "wgrad_ks"
+                      : direct ? (mfma_bf16 ? "wgrad_direct_bf16r" : "wgrad_direct")
+                      : "wgrad_lds";
+    *fam_out = fam;
+  }
+  auto pw = [](int MT, int NT, int S) { return RouteRow{"", false, PW, MT, NT, 0, false, false, S, 0, 0, false}; };
+  auto ks = [](int fam, int MT, int NT, int S, int even) {
+    return RouteRow{"", false, fam, MT, NT, 0, false, false, S, even > 0 ? even : 0, even > 0 ? S : 0, false};
+  };
+  auto direct = [](int MT, int NT, int BP, int PS, int WK, int xcd) {
+    return RouteRow{"", false, D, MT, NT, BP, WK == 4, xcd != 0, PS, 0, 0, false};
+  };
+  auto refused = [&]() { return RouteRow{"", false, L, c.MT, c.NT, c.BP, false, false, c.PS, 0, 0, true}; };
+  if (c.WK == 7) return pw(c.MT, c.NT, c.PS);
+  if (c.WK == 8) return ks(PK, c.MT, c.NT, c.PS, c.BP);
+  if (c.WK == 9) return ks(KS, c.MT, c.NT, c.PS, c.BP);
+  if (dy_padded && (c.WK == 1 || c.WK == 14 || c.WK == 101 || c.WK == 114) && (c.BP == 128 || c.BP == 256))
+    return direct(c.MT, c.NT, c.BP, c.PS, (c.WK % 100) == 14 ? 4 : 1, c.WK >= 100);
+  if (!(c.WK != 14 && c.WK < 100)) return refused();
+  if (c.WK == 0) c.WK = 1;
+  if (!(c.BP == 64 || c.BP == 128)) return refused();
+  if (!(c.WK == 1 || (c.WK == 4 && c.NT == 1))) return refused();
+  return RouteRow{"", false, L, c.MT, c.NT, c.BP, c.WK == 4, false, c.PS, 0, 0, false};
+}
+
+static int check_routes() {
+  for (const RouteRow& w : kRoutes) {
+    E2Tiling t;
+    CHECK(e2_parse_tiling(w.s, &t) && e2_wgrad_candidate(t), "'%s': five integers", w.s);
+    const E2WgradRoute r = e2_wgrad_route(t.v, w.padded);
+    if (same(r, w, w.s, w.padded)) return 1;
+    // the table itself, for the Python side (test_conv_host.py compares tiling.wgrad_route with it)
+    printf("route\t%s\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", w.s, (int)w.padded,
+           e2_wgrad_family_name(r, false), e2_wgrad_family_name(r, true), w.MT, w.NT, w.BP,
+           (int)w.wave_split, (int)w.xcd, w.splits, w.bands, w.groups, (int)w.refused);
+  }
+  // the names e2_last_launch has for the families
+  {
+    E2WgradRoute r;
+    const char* f32[] = {"wgrad_lds", "wgrad_direct", "pw_wgrad", "pw_wgrad_ks", "wgrad_ks"};
+    const int fam[] = {L, D, PW, PK, KS};
+    for (int i = 0; i < 5; ++i) {
+      r.family = fam[i];
+      CHECK(!strcmp(e2_wgrad_family_name(r, false), f32[i]), "name of family %d", fam[i]);
+      CHECK(!strcmp(e2_wgrad_family_name(r, true), fam[i] == D ? "wgrad_direct_bf16r" : f32[i]), "bf16 name of family %d", fam[i]);
+    }
+  }
+  // ... and the whole grid against the chain the route replaced
+  int cells = 0, differences = 0;
+  std::vector<int> WKs;
+  for (int w = -1; w <= 15; ++w) WKs.push_back(w);
+  for (int w = 99; w <= 115; ++w) WKs.push_back(w);
+  for (int MT : {1, 7}) for (int NT : {1, 2, 4}) for (int WK : WKs)
+    for (int BP : {0, 1, 3, 64, 128, 256, 512}) for (int PS : {0, 1, 8}) for (int padded = 0; padded < 2; ++padded)
+      for (int bf = 0; bf < 2; ++bf) {
+        const int v[5] = {MT, NT, WK, BP, PS};
+        const char* fam = nullptr;
+        const RouteRow w = old_chain(WCfg{MT, NT, WK, BP, PS}, padded != 0, bf != 0, &fam);
+        const E2WgradRoute r = e2_wgrad_route(v, padded != 0);
+        char s[64];
+        snprintf(s, sizeof s, "%d,%d,%d,%d,%d", MT, NT, WK, BP, PS);
+        ++cells;
+        if (strcmp(fam, e2_wgrad_family_name(r, bf != 0))) { ++differences; printf("FAILED '%s' padded %d: name %s\n", s, padded, fam); }
+        if (same(r, w, s, padded)) ++differences;
+      }
+  CHECK(cells == 2 * 3 * 34 * 7 * 3 * 2 * 2 && differences == 0, "%d differences in %d cells", differences, cells);
+  printf("grid\t%d\t%d\n", cells, differences);
+  return 0;
+}
+
+// ---- the limits of the K-contiguous weight-gradient GEMMs ---------------------------------------
+static bool says(const char* msg, const char* word) { return msg && strstr(msg, word); }
+
+static int check_limits() {
+  static float X[16], Y[16], DW[16];
+  // a dense 1x1x1 problem: (2, 5, 3, 7, 9) -> 6 channels
+  const e2_tensor5 xd = e2_dense_view(X, 2, 5, 3, 7, 9), yd = e2_dense_view(Y, 2, 6, 3, 7, 9);
+  const WgradArgs pw = wgrad_args(xd, yd, DW, 1, 1, 1, 0, 1);
+  CHECK(e2_pw_wgrad_limit(pw, false, 0) == nullptr && e2_pw_wgrad_limit(pw, false, 128) == nullptr, "dense 1x1x1");
+  CHECK(says(e2_pw_wgrad_limit(pw, true, 0), "bf16"), "1x1x1, bf16 mode");
+  CHECK(says(e2_wgrad_ks_limit(pw, false, 128), "taps"), "1x1x1 is no kernel with taps");
+  {
+    WgradArgs a = pw;
+    a.upR = 8;                                       // UpConv rows: the launcher's Cout % R, no limit here
+    CHECK(e2_pw_wgrad_limit(a, false, 0) == nullptr, "1x1x1, upR = 8");
+    a = pw; a.kw = 3;
+    CHECK(says(e2_pw_wgrad_limit(a, false, 0), "1x1x1"), "taps");
+    a = pw; a.xsZ = (7 + 3) * 9;                     // a crop that keeps the rows but not the planes
+    CHECK(says(e2_pw_wgrad_limit(a, false, 0), "dense channel planes"), "x planes not dense");
+    a = pw; a.xsY = 11; a.xsZ = 7 * 11;              // ... and one that keeps neither
+    CHECK(says(e2_pw_wgrad_limit(a, false, 0), "dense channel planes"), "x rows not dense");
+    a = pw; a.dsZ = 7 * 9 + 1;
+    CHECK(says(e2_pw_wgrad_limit(a, false, 0), "dense channel planes"), "dy planes not dense");
+    a = pw; a.dsY = 10;
+    CHECK(says(e2_pw_wgrad_limit(a, false, 0), "dense channel planes"), "dy rows not dense");
+  }
+  // a kernel with taps: x (1, 2, 2, 10, 32), kernel (1, 3, 3) -> dy (1, 4, 2, 8, 30) inside its
+  // padded buffer (1, 4, 2, 12, 32 + 2) at the input's row pitch 32
+  const e2_tensor5 xk = e2_dense_view(X, 1, 2, 2, 10, 32);
+  const e2_tensor5 yk{Y, 1, 4, 2, 8, 30, 4 * 2 * 384, 2 * 384, 384, 32};
+  const WgradArgs ks = wgrad_args(xk, yk, DW, 1, 3, 3, 0, 1);
+  CHECK(e2_wgrad_ks_limit(ks, false, 128) == nullptr && e2_wgrad_ks_limit(ks, false, 4096) == nullptr, "taps, padded, slack");
+  CHECK(says(e2_wgrad_ks_limit(ks, false, 0), "e2_set_input_slack"), "slack 0");
+  CHECK(says(e2_wgrad_ks_limit(ks, false, 127), "e2_set_input_slack"), "slack 127");
+  CHECK(says(e2_wgrad_ks_limit(ks, true, 128), "bf16"), "taps, bf16 mode");
+  CHECK(says(e2_pw_wgrad_limit(ks, false, 128), "1x1x1"), "taps are no 1x1x1 kernel");
+  {
+    WgradArgs a = ks;
+    a.dy_padded = 0;
+    CHECK(says(e2_wgrad_ks_limit(a, false, 128), "zero-padded"), "dy not padded");
+    a = ks; a.upR = 8;
+    CHECK(says(e2_wgrad_ks_limit(a, false, 128), "taps"), "upR = 8");
+    a = ks; a.dsY = 34;                              // the gradient's own dense pitch
+    CHECK(says(e2_wgrad_ks_limit(a, false, 128), "pitch"), "row pitch of dy and x differ");
+    a = ks; a.xsZ = 10 * 32 - 1;                     // planes overlap by one float
+    CHECK(says(e2_wgrad_ks_limit(a, false, 128), "overlap"), "overlapping planes");
+    a = ks; a.xsC = 2 * 320 - 1;                     // ... channels
+    CHECK(says(e2_wgrad_ks_limit(a, false, 128), "overlap"), "overlapping channels");
+    a = ks; a.dsC = -1;
+    CHECK(says(e2_wgrad_ks_limit(a, false, 128), "32-bit"), "negative channel stride");
+    // (kh - 1) * pitch + kw - 1 zeros behind a plane: kernel (1, 2, 2), pitch 29 -> 30, pitch 30 -> 31
+    for (int pitch = 29; pitch <= 30; ++pitch) {
+      const e2_tensor5 x2 = e2_dense_view(X, 1, 2, 2, 9, pitch);
+      const e2_tensor5 y2{Y, 1, 4, 2, 8, pitch - 1, 4 * 2 * 10 * pitch, 2 * 10 * pitch, 10 * pitch, pitch};
+      const WgradArgs b = wgrad_args(x2, y2, DW, 1, 2, 2, 0, 1);
+      CHECK((b.kh - 1) * b.xsY + b.kw - 1 == pitch + 1, "zeros");
+      if (pitch == 29) CHECK(says(e2_wgrad_ks_limit(b, false, 128), "31 zeros"), "30 zeros behind a plane");
+      else CHECK(e2_wgrad_ks_limit(b, false, 128) == nullptr, "31 zeros behind a plane");
+    }
+    // 32-bit byte offsets inside a sample: (Cout * dsC + Do * dsZ + K) * 4 + 256 just under / at 2^32
+    const int64_t K = 7 * 32 + 30, rest = 2 * 384 + K;
+    a = ks; a.Cout = 1; a.dsC = ((int64_t)1 << 30) - 64 - 1 - rest;
+    CHECK((a.dsC + rest) * 4 + 256 == ((int64_t)1 << 32) - 4, "just under");
+    CHECK(e2_wgrad_ks_limit(a, false, 128) == nullptr, "gradient sample just under the 32-bit limit");
+    a.dsC += 1;
+    CHECK(says(e2_wgrad_ks_limit(a, false, 128), "32-bit"), "gradient sample at the 32-bit limit");
+    // ... and of x: (Cin * xsC + Din * xsZ) * 4 + 256
+    a = ks; a.Cin = 1; a.xsC = ((int64_t)1 << 30) - 64 - 1 - 2 * 320;
+    CHECK(e2_wgrad_ks_limit(a, false, 128) == nullptr, "input sample just under the 32-bit limit");
+    a.xsC += 1;
+    CHECK(says(e2_wgrad_ks_limit(a, false, 128), "32-bit"), "input sample at the 32-bit limit");
+  }
+  return 0;
+}
+
 int main() {
   if (check_grammar()) return 1;
   if (check_builders()) return 1;
+  if (check_routes()) return 1;
+  if (check_limits()) return 1;
   printf("ok %d\n", g_checks);
   return 0;
 }

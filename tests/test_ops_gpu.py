@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from elektronn2_amd import tiling
 from oracle import e2_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -665,7 +666,8 @@ def test_conv3d_pointwise_wgrad_gemm(ctx, force, Ci, Co, N, sp):
     dyp = flat[:dy.size].view(dy.shape)                   # is the gradient itself + its slack)
     dyp.copy_(dev(dy))
     dw = torch.full((Co, Ci) + k, float("nan"), device="cuda")
-    fam = "pw_wgrad" if force.split(",")[2] == "7" else "pw_wgrad_ks"
+    fam = tiling.wgrad_route(tiling.parse('wgrad', force), True).family
+    assert fam in ("pw_wgrad", "pw_wgrad_ks")
     fb0 = ctx.tiling_fallbacks()
     ctx.set_tiling("wgrad", force)
     ctx.allowed_fallbacks = 2                 # (the two cropped views at the end)
