@@ -247,6 +247,8 @@ def _load():
         "e2_adam_pack_step": (C.c_int, [vp, fp, fp, fp, fp, vp, i, i, vp, i, fp, fp, C.c_float, i, sz]),
         "e2_adam_step_ex": (C.c_int, [vp, fp, fp, fp, fp, sz, vp, fp, i, fp, fp, C.c_float, i]),
         "e2_sgd_step_ex": (C.c_int, [vp, fp, fp, fp, sz, vp, fp, i, fp, fp, C.c_float, i]),
+        "e2_adagrad_step_ex": (C.c_int, [vp, fp, fp, fp, sz, vp, fp, i, fp, fp, C.c_float, i]),
+        "e2_adadelta_step_ex": (C.c_int, [vp, fp, fp, fp, fp, sz, vp, fp, i, fp, fp, C.c_float, i]),
         "e2_step_prologue": (C.c_int, [vp, fp, i, C.c_size_t, fp, fp, i, fp, i, vp]),
         "e2_graph_begin": (C.c_int, [vp]),
         "e2_graph_end": (C.c_int, [vp, C.POINTER(vp)]),
@@ -1196,6 +1198,22 @@ class Context:
                                  C.c_void_p(seg_off.data_ptr()), _fp(seg_reg),
                                  seg_reg.numel(), _fp(hyper), _fp(gdiv), float(gmul),
                                  int(bool(zero_g))), "e2_sgd_step_ex")
+
+    def adagrad_step(self, p, g, h, seg_off, seg_reg, hyper, gdiv=None, gmul=1.0, zero_g=False):
+        """h' = h + c g^2 (c = 2 at t = 0, else 1), p' = p - lr / sqrt(h') (g + wd r p); an element
+        whose h' is 0 is left unchanged; t in hyper[4] advances (e2hip.h: e2_adagrad_step_ex)"""
+        _chk(_lib.e2_adagrad_step_ex(self.h, _fp(p), _fp(g), _fp(h), p.numel(),
+                                     C.c_void_p(seg_off.data_ptr()), _fp(seg_reg),
+                                     seg_reg.numel(), _fp(hyper), _fp(gdiv), float(gmul),
+                                     int(bool(zero_g))), "e2_adagrad_step_ex")
+
+    def adadelta_step(self, p, g, s, d, seg_off, seg_reg, hyper, gdiv=None, gmul=1.0, zero_g=False):
+        """s' = mom s + (1 - mom) g^2, dir = g sqrt(d + eps) / sqrt(s + eps) on the old s and d,
+        d' = mom d + (1 - mom) dir^2, p' = p - lr (dir + wd mult p) (e2hip.h: e2_adadelta_step_ex)"""
+        _chk(_lib.e2_adadelta_step_ex(self.h, _fp(p), _fp(g), _fp(s), _fp(d), p.numel(),
+                                      C.c_void_p(seg_off.data_ptr()), _fp(seg_reg),
+                                      seg_reg.numel(), _fp(hyper), _fp(gdiv), float(gmul),
+                                      int(bool(zero_g))), "e2_adadelta_step_ex")
 
     # ---- first launch of a step that may stand k times in one graph (e2hip.h: e2_step_prologue) ----
     def step_prologue(self, state, ring=None, dst=None, src=None, hist=None):

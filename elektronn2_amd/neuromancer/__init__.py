@@ -8,6 +8,6 @@ from .neural import (Conv, UpConv, Pool, Crop, Pad, AutoMerge, UpConvMerge, Frag
                      LRN)
 from .loss import (Softmax, MultinoulliNLL, MalisNLL, SquaredLoss, AbsLoss, BinaryNLL,
                    GaussianNLL, AggregateLoss, Classification, Errors)
-from .optimiser import Optimiser, SGD, Adam
+from .optimiser import Optimiser, SGD, AdaGrad, AdaDelta, Adam
 from .model import Model, modelload, params_from_model_file
 from .options import set_plan_options, plan_options

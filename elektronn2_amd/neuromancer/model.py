@@ -45,6 +45,31 @@ class _CircularBuffer(object):
         return float(np.mean(self.buf)) if self.buf else 0.0
 
 
+class _Optimisers(dict):
+    """``Model.optimisers``: the four optimisers of the reference by name.  SGD and Adam are made
+    with the model, as they always were, and are what a fresh model lists; AdaGrad and AdaDelta
+    are made -- and listed from then on -- the first time they are asked for (``[name]``,
+    ``get``), so a model that never trains with them carries nothing of theirs, neither into
+    memory nor into its checkpoints.  ``name in optimisers`` holds for all four."""
+    ON_DEMAND = dict(AdaGrad=optimiser.AdaGrad, AdaDelta=optimiser.AdaDelta)
+
+    def __init__(self, opt_init):
+        dict.__init__(self, SGD=optimiser.SGD(*opt_init), Adam=optimiser.Adam(*opt_init))
+        self._opt_init = opt_init
+
+    def __missing__(self, name):
+        if name not in self.ON_DEMAND:
+            raise KeyError(name)
+        self[name] = self.ON_DEMAND[name](*self._opt_init)
+        return self[name]
+
+    def __contains__(self, name):
+        return dict.__contains__(self, name) or name in self.ON_DEMAND
+
+    def get(self, name, default=None):
+        return self[name] if name in self else default
+
+
 class GraphManager(object):
     """graphmanager.py:192-313, reduced to the registry."""
 
@@ -173,9 +198,9 @@ class Model(GraphManager):
                                                    step='grad')
             extras = list(self.debug_outputs)
             opt_init = (inp, self.loss_node, self.trainable_params, extras, self)
-            # AdaGrad / AdaDelta are not used by any BASELINE config
-            self.optimisers = dict(SGD=optimiser.SGD(*opt_init),
-                                   Adam=optimiser.Adam(*opt_init))
+            # all four of the reference (model.py:196-199): SGD and Adam now, AdaGrad and
+            # AdaDelta when they are first asked for (_Optimisers)
+            self.optimisers = _Optimisers(opt_init)
 
     # ------------------------------------------------------------------ device arena
     def ensure_arena(self, ctx):
@@ -381,7 +406,7 @@ class Model(GraphManager):
         The reference pickles ``(node descriptors, designations)`` -- class references,
         ctor args and parameter values -- and drops the optimiser state.  Here one ``.npz``
         written under exactly the given name holds: every parameter value (``p/<node>/
-        <param>``), the optimiser state (Adam m, s, t; SGD last_dir: ``o/<opt>/...``), the
+        <param>``), the optimiser state (Adam m, s, t; SGD last_dir; AdaGrad h, t; AdaDelta s, d: ``o/<opt>/...``), the
         iteration count, and a JSON graph description (class NAME, args, kwargs per node +
         the designations) from which ``modelload`` re-executes the constructors, as
         graphmanager.py:120-189 does, without unpickling code."""

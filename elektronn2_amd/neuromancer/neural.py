@@ -867,7 +867,7 @@ class Conv(NeuralLayer):
             pre = plan.scratch.get((self, 'pre'), plan.out[self])
             ctx.batchnorm_act_fwd(lin, plan.param(self.gamma), plan.param(self.b),
                                   plan.param(self.mean), plan.param(self.std), train,
-                                  train and plan.step in ('SGD', 'Adam'), self._lin_act(),
+                                  train and plan.updates_params(), self._lin_act(),
                                   pre, plan.scratch[self, 'bn_save'])
             if not self._plain_act():
                 ctx.act_fwd(pre, None, self.activation_func, plan.out[self])
@@ -1213,7 +1213,7 @@ class Perceptron(NeuralLayer):
             pre = plan.scratch.get((self, 'pre'), plan.out[self])
             ctx.batchnorm_act_fwd(lin, plan.param(self.gamma), plan.param(self.b),
                                   plan.param(self.mean), plan.param(self.std), train,
-                                  train and plan.step in ('SGD', 'Adam'), self._lin_act(),
+                                  train and plan.updates_params(), self._lin_act(),
                                   pre, plan.scratch[self, 'bn_save'])
             if not self._plain_act():
                 ctx.act_fwd(pre, None, self.activation_func, plan.out[self])
@@ -1405,7 +1405,7 @@ class UpConv(Conv):
             train = self.batch_normalisation == 'train'
             plan.ctx.batchnorm_act_fwd(dst, plan.param(self.gamma), plan.param(self.b),
                                        plan.param(self.mean), plan.param(self.std), train,
-                                       train and plan.step in ('SGD', 'Adam'), self._lin_act(),
+                                       train and plan.updates_params(), self._lin_act(),
                                        pre, plan.scratch[self, 'bn_save'])
         if not self._plain_act():
             plan.ctx.act_fwd(pre, None, self.activation_func, plan.out[self])

@@ -1,15 +1,18 @@
-"""SGD and Adam with the reference's update rules and globals
-(elektronn2/neuromancer/optimiser.py:19-129, 135-165, 273-334).
+"""SGD, AdaGrad, AdaDelta and Adam with the reference's update rules and globals
+(elektronn2/neuromancer/optimiser.py:19-129, 135-165, 168-214, 222-264, 273-334).
 
 ``lr`` / ``mom`` / ``wd`` are CLASS-level parameters shared by all optimisers
 (optimiser.py:19-29); ``beta2`` belongs to Adam.  The update itself is one fused
 HIP launch over the model's flat parameter arena (``e2_adam_step`` /
-``e2_sgd_step``); the hyper-parameters live in a small device array that is
-refreshed from the host values before every step, so learning-rate schedules
-work under hipGraph replay.  Adam's step counter ``t`` and bias factor are kept
-on the device.  The 3-deep parameter rotation for ``repair()``
-(optimiser.py:103-118) is not kept (its only call site is commented out in the
-reference, trainer.py:207).  AdaGrad / AdaDelta: not used by any BASELINE config.
+``e2_sgd_step`` / ``e2_adagrad_step_ex`` / ``e2_adadelta_step_ex``); the
+hyper-parameters live in a small device array that is refreshed from the host
+values before every step, so learning-rate schedules work under hipGraph replay.
+The step counter ``t`` of Adam and AdaGrad (and Adam's bias factor) is kept on the
+device.  The 3-deep parameter rotation for ``repair()`` (optimiser.py:103-118) is
+not kept (its only call site is commented out in the reference, trainer.py:207);
+what ``repair()`` resets of an optimiser's own state is ``clear_last_dir()``.
+AdaGrad leaves an element whose squared-gradient sum is still 0 unchanged, where
+the reference divides by sqrt(0) (class AdaGrad).
 """
 from __future__ import annotations
 
@@ -18,7 +21,7 @@ import numpy as np
 from . import graphutils
 from .variables import VariableParam
 
-__all__ = ['Optimiser', 'SGD', 'Adam']
+__all__ = ['Optimiser', 'SGD', 'AdaGrad', 'AdaDelta', 'Adam']
 
 
 class Optimiser(object):
@@ -240,7 +243,30 @@ class SGD(Optimiser):
             self._apply(d)
 
 
-class Adam(Optimiser):
+class _StepCounter(object):
+    """the step counter t of Adam and AdaGrad: hyper[4] on the device (a replayed graph cannot be
+    handed a new value), parked in ``_pending_t`` while the device array does not exist"""
+    _pending_t = None
+
+    @property
+    def t(self):
+        if self._hyper is None:
+            return 0.0 if self._pending_t is None else float(self._pending_t)
+        return float(self._hyper[4].item())
+
+    def _apply_pending_hyper(self):
+        if self._pending_t is not None:
+            self._hyper[4] = float(self._pending_t)
+            self._pending_t = None
+
+    def _load_t(self, d):
+        if 't' in d:
+            self._pending_t = float(np.asarray(d['t']))
+            if self._hyper is not None:
+                self._apply_pending_hyper()
+
+
+class Adam(_StepCounter, Optimiser):
     """optimiser.py:273-334: eps = 1e-5 INSIDE the sqrt, bias factor
     sqrt(1-beta2^t)/(1-mom^t), L2 term outside the adaptive scaling."""
     step_name = 'Adam'
@@ -277,12 +303,6 @@ class Adam(Optimiser):
                            self.momentum, self.squared_accum, m.seg_off, m.seg_reg,
                            self._hyper, **self._grad_scaling(plan))
 
-    @property
-    def t(self):
-        if self._hyper is None:
-            return 0.0 if self._pending_t is None else float(self._pending_t)
-        return float(self._hyper[4].item())
-
     def state_dict(self):
         if self.momentum is None:
             # loaded but not stepped yet (modelload(f) followed by save()): the moments and
@@ -306,11 +326,6 @@ class Adam(Optimiser):
             self.momentum.copy_(torch.from_numpy(m))
             self.squared_accum.copy_(torch.from_numpy(s))
 
-    def _apply_pending_hyper(self):
-        if self._pending_t is not None:
-            self._hyper[4] = float(self._pending_t)
-            self._pending_t = None
-
     def load_state_dict(self, d):
         """m, s and the step counter t.  The device buffers are created lazily by the
         first step; a state loaded before that (``create_model(); modelload(f, model)``)
@@ -320,7 +335,136 @@ class Adam(Optimiser):
             self._pending = {k: d[k] for k in ('m', 's') if k in d} or None
         else:
             self._apply(d)
-        if 't' in d:
-            self._pending_t = float(np.asarray(d['t']))
-            if self._hyper is not None:
-                self._apply_pending_hyper()
+        self._load_t(d)
+
+
+class AdaGrad(_StepCounter, Optimiser):
+    """h' = h + g^2 ; p' = p - lr / sqrt(h') * (g + wd*p [where apply_reg])  (optimiser.py:168-214).
+
+    * The reference's first call runs ``init_func`` (h += g^2 from one gradient evaluation of
+      the same batch) before the step adds g^2 again (optimiser.py:200-214).  Both gradients
+      are the same, so here the first step (t == 0) adds 2 g^2 in its one launch.  (With
+      dropout the reference draws new gates for its second evaluation; here the step's own
+      gradient counts twice.)
+    * optimiser.py:187-189 has no ``apply_reg > 1`` branch: batch norm's gamma (multiplier 3)
+      decays like any weight under AdaGrad.
+    * THE ONE DEPARTURE: an element whose gradient has been exactly zero since the start has
+      h' == 0; the reference divides by sqrt(0) and writes NaN / inf into it.  Here it is
+      left unchanged and its h stays 0.
+    ``t`` counts the steps on the device, as Adam's does."""
+    step_name = 'AdaGrad'
+
+    def __init__(self, *a):
+        self.hs = None
+        self._pending = None
+        self._pending_t = None
+        super(AdaGrad, self).__init__(*a)
+
+    def _ensure_state(self, plan):
+        if self.hs is None:
+            self.hs = plan.zeros_flat(max(self.model.n_train, 4))
+        if self._pending is not None:
+            self._apply(self._pending)
+            self._pending = None
+
+    def device_update(self, plan):
+        m = self.model
+        plan.ctx.adagrad_step(m.P[:m.n_train] if m.n_train < m.P.numel() else m.P, m.G,
+                              self.hs, m.seg_off, m.seg_reg, self._hyper,
+                              **self._grad_scaling(plan))
+
+    def clear_last_dir(self):
+        """h and t back to zero: the next step is a first step again (the resettable part of
+        optimiser.py:217-220)"""
+        if self.hs is not None:
+            self.hs.zero_()
+        self._pending = None
+        self._load_t(dict(t=0.0))
+
+    def state_dict(self):
+        if self.hs is None:
+            # loaded but not stepped yet: hand the parked state on (load -> save -> load)
+            if self._pending is not None and 'h' in self._pending:
+                return {'h': np.array(self._pending['h'], dtype=np.float32), 't': np.array(self.t)}
+            return {}
+        return {'h': self.hs.cpu().numpy(), 't': np.array(self.t)}
+
+    def _apply(self, d):
+        import torch
+        if 'h' in d:
+            v = np.ascontiguousarray(d['h'], dtype=np.float32)
+            if v.size != self.hs.numel():
+                raise ValueError("AdaGrad state of %i elements does not fit this model (%i)"
+                                 % (v.size, self.hs.numel()))
+            self.hs.copy_(torch.from_numpy(v))
+
+    def load_state_dict(self, d):
+        """h and the step counter t; a state loaded before the first step is kept and applied
+        when the buffers exist, so a resumed run does not double its first gradient again"""
+        if self.hs is None:
+            self._pending = {k: d[k] for k in ('h',) if k in d} or None
+        else:
+            self._apply(d)
+        self._load_t(d)
+
+
+class AdaDelta(Optimiser):
+    """s' = mom*s + (1-mom)*g^2 ; dir = g * sqrt(d + eps) / sqrt(s + eps) on the OLD s and d ;
+    d' = mom*d + (1-mom)*dir^2 ; p' = p - lr*(dir + wd*p [*apply_reg])  (optimiser.py:222-264),
+    eps = 1e-5."""
+    step_name = 'AdaDelta'
+
+    def __init__(self, *a):
+        self.squared_accum = None
+        self.delta_accum = None
+        self._pending = None
+        super(AdaDelta, self).__init__(*a)
+
+    def _ensure_state(self, plan):
+        if self.squared_accum is None:
+            n = max(self.model.n_train, 4)
+            self.squared_accum = plan.zeros_flat(n)
+            self.delta_accum = plan.zeros_flat(n)
+        if self._pending is not None:
+            self._apply(self._pending)
+            self._pending = None
+
+    def device_update(self, plan):
+        m = self.model
+        plan.ctx.adadelta_step(m.P[:m.n_train] if m.n_train < m.P.numel() else m.P, m.G,
+                               self.squared_accum, self.delta_accum, m.seg_off, m.seg_reg,
+                               self._hyper, **self._grad_scaling(plan))
+
+    def clear_last_dir(self):
+        """both accumulators back to zero (the resettable part of optimiser.py:267-269)"""
+        if self.squared_accum is not None:
+            self.squared_accum.zero_()
+            self.delta_accum.zero_()
+        self._pending = None
+
+    def state_dict(self):
+        if self.squared_accum is None:
+            if self._pending is not None and 's' in self._pending:
+                return {'s': np.array(self._pending['s'], dtype=np.float32),
+                        'd': np.array(self._pending['d'], dtype=np.float32)}
+            return {}
+        return {'s': self.squared_accum.cpu().numpy(), 'd': self.delta_accum.cpu().numpy()}
+
+    def _apply(self, d):
+        import torch
+        if 's' in d:
+            s = np.ascontiguousarray(d['s'], dtype=np.float32)
+            dl = np.ascontiguousarray(d['d'], dtype=np.float32)
+            if s.size != self.squared_accum.numel() or dl.size != self.squared_accum.numel():
+                raise ValueError("AdaDelta state of %i elements does not fit this model (%i)"
+                                 % (s.size, self.squared_accum.numel()))
+            self.squared_accum.copy_(torch.from_numpy(s))
+            self.delta_accum.copy_(torch.from_numpy(dl))
+
+    def load_state_dict(self, d):
+        """both accumulators; a state loaded before the first step is kept and applied when the
+        buffers exist"""
+        if self.squared_accum is None:
+            self._pending = {k: d[k] for k in ('s', 'd') if k in d} or None
+        else:
+            self._apply(d)

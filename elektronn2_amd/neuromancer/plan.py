@@ -50,6 +50,11 @@ def set_mfma_dtype(dtype):
     get_ctx().set_mfma_dtype(dtype)
 
 
+# the step names that name an optimiser (optimiser.py: step_name); every other step ('grad', None)
+# leaves the parameters alone
+UPDATE_STEPS = ('SGD', 'AdaGrad', 'AdaDelta', 'Adam')
+
+
 class Plan(object):
     def __init__(self, inputs, outputs, model=None, step=None, name='', use_graph=True, options=None):
         # the host switches, SNAPSHOT at construction (options.py): what is set later -- in the
@@ -58,7 +63,7 @@ class Plan(object):
         self.opt = _options.snapshot(options)
         self.inputs = list(inputs)
         self.outputs = list(outputs)
-        self.step = step                       # None | 'SGD' | 'Adam' | 'grad'
+        self.step = step                       # None | an optimiser's step_name (UPDATE_STEPS) | 'grad'
         self.training = step is not None
         self.name = name
         self.model = model if model is not None else getattr(self.outputs[0], '_model', None)
@@ -776,8 +781,14 @@ class Plan(object):
         st = self.scratch.get((kids[0].pred, 'stats'))
         return None if st is None else st[1:2]
 
+    def updates_params(self):
+        """this plan's step ends in an optimiser launch that writes the parameters: it issues the
+        update, may leave the gradient arena clean, exchanges gradients between ranks, moves batch
+        norm's running statistics and makes the packed weight images stale"""
+        return self.step in UPDATE_STEPS
+
     def _emit_update(self):
-        if self.step in ('Adam', 'SGD'):
+        if self.updates_params():
             self.model.optimisers[self.step].device_update(self)
 
     def _upd_zeroes_g(self):
@@ -785,7 +796,7 @@ class Plan(object):
         (e2_adam_step_ex zero_g): no fill launch at the head of the backward pass.  G is
         zero on entry because the last step left it so -- or _run_device fills it first
         (Model._g_clean)."""
-        return (self.training and self.step in ('Adam', 'SGD') and bool(self.opt['zero_in_update']))
+        return (self.training and self.updates_params() and bool(self.opt['zero_in_update']))
 
     def _dp_key(self):
         """everything outside the plan that the segmentation and the captured graphs depend on:
@@ -807,7 +818,7 @@ class Plan(object):
         gradients unnormalised and put the labelled count into the slot behind the arena, the
         collectives only SUM, the optimiser kernel divides by the summed count; ('mean', 1/w)
         = plain mean, the factor applied by the optimiser kernel."""
-        if not (self.training and self.step in ('Adam', 'SGD') and self.model.dp_world() > 1
+        if not (self.training and self.updates_params() and self.model.dp_world() > 1
                 and self.opt['dp_fused_scale'] and self.model.G.is_cuda):
             return None
         if getattr(self.model, '_dp_weighted', False):
@@ -841,10 +852,10 @@ class Plan(object):
         stream (each segment is captured into its own hipGraph), ``after`` is host code
         run between two segments -- the gradient exchange of the data-parallel step, or
         the host part of a node (MALIS: Kruskal on the CPU between forward and loss)."""
-        dp = self.training and self.step in ('Adam', 'SGD') and self.model.dp_world() > 1
+        dp = self.training and self.updates_params() and self.model.dp_world() > 1
         self._dp_scale_mode = self._dp_scale_now()       # decided ONCE per segmentation
         host = [n for n in self.nodes if hasattr(n, '_plan_host')]
-        upd = self.training and self.step in ('Adam', 'SGD')
+        upd = self.training and self.updates_params()
         segs = []
         if host:
             def host_steps():
@@ -988,7 +999,7 @@ class Plan(object):
         self._calls += 1
         if self.training:
             self.model._g_clean = self._upd_zeroes_g()
-            if self.step in ('Adam', 'SGD'):       # (this step wrote P: whose images are current?)
+            if self.updates_params():       # (this step wrote P: whose images are current?)
                 self.model._img_owner = self if self._upd is not None else None
 
     def _emit_seg(self, i, emit, zero_jobs):
@@ -1152,7 +1163,7 @@ class Plan(object):
                 self._calls += k
                 self._n_runs += k
                 self.model._g_clean = self._upd_zeroes_g()
-                if self.step in ('Adam', 'SGD'):
+                if self.updates_params():
                     self.model._img_owner = self if self._upd is not None else None
         finally:
             ctx.set_stream(old)

@@ -638,6 +638,35 @@ int e2_sgd_step_ex(e2_ctx*, float* p, float* g, float* d, size_t n, const int64_
                    const float* seg_reg, int n_seg, const float* hyper, const float* gdiv,
                    float gmul, int zero_g);
 
+/* AdaGrad (optimiser.py:168-214) and AdaDelta (optimiser.py:222-264) on the same arena, segment
+ * tables, hyper array ({lr, mom, -, wd, t, -, -, arrival counter}) and gdiv / gmul / zero_g as
+ * the two above; all arithmetic float32, g' = the scaled gradient.
+ *   AdaGrad:  c = (t == 0) ? 2 : 1;  h' = h + c g'^2;  p' = p - lr / sqrt(h') (g' + wd r p);
+ *     t' = t + 1.  c: the reference's first call runs init_func (h += g^2 from one gradient
+ *     evaluation of the same batch) and then the step, which adds g^2 again (optimiser.py:
+ *     200-214); with the same batch and parameters both gradients are the same, so the first
+ *     step sees h = 2 g^2 -- one launch here, no second forward / backward pass.  (With dropout
+ *     the reference draws different gates in its two evaluations; here the step's own gradient
+ *     counts twice.)  r = 1 where the segment's multiplier is not 0, else 0: optimiser.py:187-189
+ *     has no apply_reg > 1 branch, so a multiplier of 3 decays like 1 under AdaGrad.  t lives in
+ *     hyper[4] as Adam's does; hyper[7] must be zero before the first call; hyper[5] is left
+ *     alone.  THE ONE DEPARTURE from the reference: where h' == 0 -- every gradient of the
+ *     element exactly zero since the start: a dead unit, a feature that never fired -- the
+ *     reference divides by sqrt(0) and writes NaN or +-inf into the parameter; here the element
+ *     is left unchanged and h stays 0.
+ *   AdaDelta: eps = 1e-5;  s' = mom s + (1 - mom) g'^2;  dir = g' sqrt(d + eps) / sqrt(s + eps)
+ *     with the OLD s and the OLD d, as the reference has it (optimiser.py:243-245);
+ *     d' = mom d + (1 - mom) dir^2;  p' = p - lr (dir + wd mult p), mult = the segment's
+ *     multiplier as in SGD.  No step counter: hyper is only read.
+ * Refusals as above (a NULL argument, n_seg outside 1..1024, an arena off its 16-byte
+ * boundary): nothing is written. */
+int e2_adagrad_step_ex(e2_ctx*, float* p, float* g, float* h, size_t n, const int64_t* seg_off,
+                       const float* seg_reg, int n_seg, const float* hyper,
+                       const float* gdiv, float gmul, int zero_g);
+int e2_adadelta_step_ex(e2_ctx*, float* p, float* g, float* s, float* d, size_t n,
+                        const int64_t* seg_off, const float* seg_reg, int n_seg,
+                        const float* hyper, const float* gdiv, float gmul, int zero_g);
+
 /* The Adam update of optimiser.py:301-329 that also WRITES the packed weight images of every
  * conv (what e2_conv3d_pack_multi does at the head of a step): a work-group owns a tile of one
  * weight tensor -- 32 output channels x IC input channels x the taps of one kernel plane --,

@@ -36,7 +36,7 @@ def steps_of(path, default):
     """the optimiser launch runs once per step: its call count is the number of steps in the file
     (20 + 5 until round 5; since bench.py runs several steps per graph launch the set-up adds more)"""
     for r in csv.DictReader(open(path)):
-        if short(r["Name"]) in ("adam_kernel", "sgd_kernel"):
+        if short(r["Name"]) in ("adam_kernel", "sgd_kernel", "adagrad_kernel", "adadelta_kernel"):
             return int(r["Calls"])
     return default
 
