@@ -101,6 +101,8 @@ def _load():
             "`make -C elektronn2_amd/csrc`.  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     P5 = C.POINTER(Tensor5)
+    PP5 = C.POINTER(P5)
+    PV = C.POINTER(C.c_void_p)
     PW = C.POINTER(NllWeights)
     PL = C.POINTER(LossTerm)
     vp, i, sz, fp = C.c_void_p, C.c_int, C.c_size_t, C.c_void_p
@@ -186,6 +188,13 @@ def _load():
         "e2_softmax_nll_bwd_w": (C.c_int, [vp, P5, P5, fp, P5, fp, PW]),
         "e2_softmax_nll_grouped_fwd": (C.c_int, [vp, P5, P5, P5, i, fp]),
         "e2_softmax_nll_grouped_bwd": (C.c_int, [vp, P5, P5, i, fp, P5, fp]),
+        "e2_nll_multi_fwd": (C.c_int, [vp, i, PP5, PP5, PP5, fp]),
+        "e2_nll_mix": (C.c_int, [vp, i, fp, fp, fp, fp, fp, fp]),
+        "e2_nll_multi_bwd": (C.c_int, [vp, i, PP5, PP5, fp, PP5]),
+        "e2_multihead_supported": (C.c_int, [i, i, C.POINTER(C.c_int)]),
+        "e2_multihead_fwd": (C.c_int, [vp, P5, i, PV, PV, C.POINTER(C.c_int), PP5, PP5, fp]),
+        "e2_multihead_bwd_workspace_bytes": (sz, [i, i, i, i, i, i]),
+        "e2_multihead_bwd": (C.c_int, [vp, P5, i, PV, PP5, PP5, fp, P5, i, PV, PV, C.c_void_p, sz]),
         "e2_head_fwd_w": (C.c_int, [vp, P5, fp, fp, i, P5, P5, fp, PW]),
         "e2_head_bwd_w": (C.c_int, [vp, P5, fp, P5, P5, fp, P5, i, fp, fp, fp, C.c_void_p,
                                     sz, PW]),
@@ -880,6 +889,95 @@ class Context:
         _chk(_lib.e2_softmax_nll_grouped_bwd(
             self.h, C.byref(t5(probs)), C.byref(t5(target)), int(n_indep), _fp(stats),
             C.byref(t5(dlogits)), _fp(loss_out)), "e2_softmax_nll_grouped_bwd")
+
+    # ---- K MultinoulliNLL terms under one AggregateLoss (csrc/softmax_nll.hip) ----
+    @staticmethod
+    def _views(tensors, k):
+        """a host array of k view pointers (None entries: NULL) and the descriptors it points to;
+        ``tensors`` None: a NULL array"""
+        if tensors is None:
+            return None, None
+        keep = [None if t is None else t5(t) for t in tensors]
+        arr = (C.POINTER(Tensor5) * max(len(keep), k, 1))()
+        for j, d in enumerate(keep):
+            if d is not None:
+                arr[j] = C.pointer(d)
+        return arr, keep
+
+    def nll_multi_fwd(self, logits, targets, probs, stats, k=None):
+        """one launch: probs[j] = softmax(logits[j]) and, with targets, stats[2j] += S_j,
+        stats[2j + 1] += N_j for every term j.  ``targets`` None (or all entries None):
+        probabilities only.  ``k`` defaults to len(logits)."""
+        k = len(logits) if k is None else int(k)
+        la, lk = self._views(logits, k)
+        ta, tk = self._views(targets, k)
+        pa, pk = self._views(probs, k)
+        _chk(_lib.e2_nll_multi_fwd(self.h, k, la, ta, pa, _fp(stats)), "e2_nll_multi_fwd")
+
+    def nll_mix(self, k, stats, mix, coef, term_loss, count, loss_out):
+        """one small launch: coef[j] = mix[j] / (k (N_j + 1e-5)), term_loss[j] = L_j, count[j] = N_j,
+        loss_out[0] = (1/k) sum_j mix[j] L_j; ``mix`` is read on the device"""
+        _chk(_lib.e2_nll_mix(self.h, int(k), _fp(stats), _fp(mix), _fp(coef), _fp(term_loss),
+                             _fp(count), _fp(loss_out)), "e2_nll_mix")
+
+    def nll_multi_bwd(self, probs, targets, coef, dlogits, k=None):
+        """one launch: dlogits[j] = d total / d logits[j]; dlogits[j] may alias probs[j]"""
+        k = len(probs) if k is None else int(k)
+        pa, pk = self._views(probs, k)
+        ta, tk = self._views(targets, k)
+        da, dk = self._views(dlogits, k)
+        _chk(_lib.e2_nll_multi_bwd(self.h, k, pa, ta, _fp(coef), da), "e2_nll_multi_bwd")
+
+    # ---- K classifier heads on one trunk, fused (csrc/multihead.hip) ----
+    @staticmethod
+    def _ptrs(tensors, k):
+        """a host array of k device pointers (contiguous float32 tensors; None: NULL)"""
+        if tensors is None:
+            return None
+        arr = (C.c_void_p * max(len(tensors), k, 1))()
+        for j, t in enumerate(tensors):
+            v = _fp(t)
+            arr[j] = None if v is None else v.value
+        return arr
+
+    @staticmethod
+    def multihead_supported(cin, ncls):
+        ncls = [int(c) for c in ncls]
+        return bool(_lib.e2_multihead_supported(int(cin), len(ncls),
+                                                (C.c_int * max(len(ncls), 1))(*ncls)))
+
+    def multihead_fwd(self, x, w, bias, targets, probs, stats, k=None):
+        """one launch: probs[j] = softmax(w[j] x + bias[j]) for every head j of the trunk ``x``
+        and, with targets, stats[2j] += S_j, stats[2j + 1] += N_j.  ``w[j]``: (ncls_j, cin) dense"""
+        k = len(probs) if k is None else int(k)
+        ncls = (C.c_int * max(len(probs), k, 1))(*[int(p.shape[1]) for p in probs])
+        ta, tk = self._views(targets, k)
+        pa, pk = self._views(probs, k)
+        xd = t5(x)
+        _chk(_lib.e2_multihead_fwd(self.h, C.byref(xd), k, self._ptrs(w, k), self._ptrs(bias, k),
+                                   ncls, ta, pa, _fp(stats)), "e2_multihead_fwd")
+
+    @staticmethod
+    def multihead_bwd_ws_bytes(x_shape, sum_ncls):
+        n, cin, d, h, w = (int(v) for v in x_shape)
+        return int(_lib.e2_multihead_bwd_workspace_bytes(n, cin, int(sum_ncls), d, h, w))
+
+    def multihead_bwd(self, x, w, probs, targets, coef, dx, accumulate_dx, dw, dbias, ws, k=None,
+                      ws_bytes=None):
+        """one launch (+ the reduce): dx (=|+=) sum_j w[j]^T dlogits_j, dw[j] / dbias[j] += their
+        gradients; ``ws``: multihead_bwd_ws_bytes(x.shape, sum ncls) bytes"""
+        k = len(probs) if k is None else int(k)
+        pa, pk = self._views(probs, k)
+        ta, tk = self._views(targets, k)
+        xd = t5(x)
+        dxd = t5(dx) if dx is not None else None
+        _chk(_lib.e2_multihead_bwd(
+            self.h, C.byref(xd), k, self._ptrs(w, k), pa, ta, _fp(coef),
+            C.byref(dxd) if dxd is not None else None, 1 if accumulate_dx else 0,
+            self._ptrs(dw, k), self._ptrs(dbias, k),
+            C.c_void_p(ws.data_ptr()) if ws is not None else None,
+            ws.numel() * ws.element_size() if ws_bytes is None else int(ws_bytes)),
+            "e2_multihead_bwd")
 
     def fill_multi(self, ptrs_dev, counts_dev, n, value=0.0):
         """one launch that fills n flat regions (int64 device tensors of pointers / counts)"""

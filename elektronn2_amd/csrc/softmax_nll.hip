@@ -34,14 +34,14 @@ __global__ void softmax_nll_fwd_w_kernel(View5 lg, View5 tg, View5 pr,
 __global__ void softmax_nll_bwd_kernel(View5 pr, View5 tg, const float* __restrict__ stats,
                                        View5 dl, float* __restrict__ loss_out, int sum_mode,
                                        float* __restrict__ count_out) {
-  constexpr bool WT = false;
+  constexpr bool WT = false, COEF = false;
   const NllW wt{};
 #include "softmax_nll_bwd_body.hpp"
 }
 __global__ void softmax_nll_bwd_w_kernel(View5 pr, View5 tg, const float* __restrict__ stats,
                                          View5 dl, float* __restrict__ loss_out, int sum_mode,
                                          float* __restrict__ count_out, NllW wt) {
-  constexpr bool WT = true;
+  constexpr bool WT = true, COEF = false;
 #include "softmax_nll_bwd_body.hpp"
 }
 
@@ -90,9 +90,76 @@ __global__ __launch_bounds__(256) void softmax_nll_grouped_fwd_kernel(View5 lg_a
 __global__ __launch_bounds__(256) void softmax_nll_grouped_bwd_kernel(
     View5 pr_all, View5 tg_all, const float* __restrict__ stats, View5 dl_all, int k,
     float* __restrict__ loss_out, int sum_mode, float* __restrict__ count_out) {
-  constexpr bool WT = false;
+  constexpr bool WT = false, COEF = false;
   const NllW wt{};
   const View5 pr = group_of(pr_all, k), dl = group_of(dl_all, k), tg = group_of(tg_all, 1);
+#include "softmax_nll_bwd_body.hpp"
+}
+
+// ---------------------------------------------------------------------------
+// K MultinoulliNLL terms under one AggregateLoss (loss.py:261-347 per term, 1357-1363 for the
+// mix), each over a softmax of its own (n_indep = 1, sparse target): e2_nll_multi_fwd /
+// e2_nll_mix / e2_nll_multi_bwd (include/e2hip.h).
+// ---------------------------------------------------------------------------
+// The term is grid dimension y over the same per-thread body: work-group (bx, j, n) handles 256
+// positions of term j, whose three views arrive by value in the kernel arguments (work-group-
+// uniform index: scalar loads, no register array).  The terms may differ in class count and in
+// spatial size; grid.x covers the largest and the work-groups past a smaller term's positions
+// leave at once.  stats = {S_0, N_0, S_1, N_1, ...}: every term has its own pair and so its own
+// normaliser (unlike the groups above).
+struct NllMultiV {
+  View5 a[E2_MAX_LOSS_TERMS];     // forward: logits    backward: probs
+  View5 t[E2_MAX_LOSS_TERMS];     // targets
+  View5 b[E2_MAX_LOSS_TERMS];     // forward: probs     backward: dlogits
+};
+
+template <bool HAS_T>
+__global__ __launch_bounds__(256) void nll_multi_fwd_kernel(NllMultiV v,
+                                                            float* __restrict__ stats_all) {
+  constexpr bool WT = false;
+  const NllW wt{};
+  const int j = blockIdx.y;
+  const View5 lg = v.a[j], tg = v.t[j], pr = v.b[j];
+  if (blockIdx.x * 256L >= (long)lg.d * lg.h * lg.w) return;      // (the whole work-group)
+  float* const stats = stats_all + 2 * j;
+#include "softmax_nll_fwd_body.hpp"
+}
+
+// one work-group: term values, counts, gradient coefficients and the total.  mix is read here,
+// on the device: a captured launch follows its contents.
+__global__ void nll_mix_kernel(int k, const float* __restrict__ stats,
+                               const float* __restrict__ mix, float* __restrict__ coef,
+                               float* __restrict__ term_loss, float* __restrict__ count,
+                               float* __restrict__ loss_out) {
+  const int j = threadIdx.x;
+  __shared__ float part[E2_MAX_LOSS_TERMS];
+  if (j < k) {
+    const float S = stats[2 * j], N = stats[2 * j + 1], w = mix[j];
+    const float L = S / (N + E2_EPS_NLL);
+    term_loss[j] = L;
+    count[j] = N;
+    coef[j] = w / ((float)k * (N + E2_EPS_NLL));
+    part[j] = w * L;
+  }
+  __syncthreads();
+  if (j == 0) {
+    float tot = 0.f;
+    for (int i = 0; i < k; ++i) tot += part[i];      // (fixed order)
+    loss_out[0] = tot / (float)k;
+  }
+}
+
+// coef[j] = w_j / (K (N_j + eps)) takes the place of 1 / (n_lab + eps) in the body
+__global__ __launch_bounds__(256) void nll_multi_bwd_kernel(NllMultiV v,
+                                                            const float* __restrict__ coef) {
+  constexpr bool WT = false, COEF = true;
+  const NllW wt{};
+  const int j = blockIdx.y;
+  const View5 pr = v.a[j], tg = v.t[j], dl = v.b[j];
+  const float* const stats = coef + j;
+  float* const loss_out = nullptr;
+  float* const count_out = nullptr;
+  constexpr int sum_mode = 0;
 #include "softmax_nll_bwd_body.hpp"
 }
 
@@ -294,6 +361,91 @@ extern "C" int e2_malis_nll(e2_ctx* ctx, const e2_tensor5* probs, const float* p
   dim3 grid((unsigned)((S + 255) / 256), (unsigned)(p.c / 2), 1);
   hipLaunchKernelGGL(malis_nll_kernel, grid, dim3(256), 0, ctx->stream, p, pos, neg, norm, d,
                      dlogits ? 1 : 0, loss_sum);
+  E2_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- K NLL terms under one mix: the entry points ------------------------------------------
+// (sum mode, e2_set_loss_grad_mode, has ONE count slot: K counts do not fit -- an error)
+static int nll_multi_pack(e2_ctx* ctx, const char* who, int k, const e2_tensor5* const* a,
+                          const char* an, const e2_tensor5* const* targets,
+                          const e2_tensor5* const* b, const char* bn, bool need_targets,
+                          NllMultiV* v, bool* has_t, long* s_max) {
+  E2_REQUIRE(ctx, "%s: null context", who);
+  E2_REQUIRE(!ctx->loss_sum_mode, "%s: not available in loss-gradient sum mode (one count slot "
+             "cannot hold the terms' counts)", who);
+  E2_REQUIRE(k >= 1 && k <= E2_MAX_LOSS_TERMS, "%s: %d terms, 1..%d are supported", who, k,
+             E2_MAX_LOSS_TERMS);
+  E2_REQUIRE(a && b, "%s: null argument", who);
+  int n_t = 0;
+  for (int j = 0; j < k; ++j) n_t += (targets && targets[j]) ? 1 : 0;
+  E2_REQUIRE(n_t == 0 || n_t == k, "%s: %d of %d terms have a target (all or none)", who, n_t, k);
+  E2_REQUIRE(n_t == k || !need_targets, "%s: null target", who);
+  *has_t = n_t == k;
+  *s_max = 0;
+  for (int j = 0; j < k; ++j) {
+    char name[96];
+    snprintf(name, sizeof name, "%s[%d]", who, j);
+    if (int rc = nll_views_ok(name, a[j], an, b[j], bn, *has_t ? targets[j] : nullptr, 1))
+      return rc;
+    E2_REQUIRE(a[j]->n == a[0]->n, "%s: term %d has batch %d, term 0 has %d", who, j, a[j]->n,
+               a[0]->n);
+    const long S = (long)a[j]->d * a[j]->h * a[j]->w;
+    E2_REQUIRE((S + 255) / 256 < (1L << 31), "%s: tensor too large", who);
+    *s_max = S > *s_max ? S : *s_max;
+    v->a[j] = mk(a[j]);
+    v->b[j] = mk(b[j]);
+    v->t[j] = *has_t ? mk(targets[j]) : View5{};
+  }
+  return 0;
+}
+
+extern "C" int e2_nll_multi_fwd(e2_ctx* ctx, int k, const e2_tensor5* const* logits,
+                                const e2_tensor5* const* targets,
+                                const e2_tensor5* const* probs, float* stats) {
+  NllMultiV v{};
+  bool has_t;
+  long s_max;
+  if (int rc = nll_multi_pack(ctx, "nll_multi_fwd", k, logits, "logits", targets, probs, "probs",
+                              false, &v, &has_t, &s_max))
+    return rc;
+  E2_REQUIRE(!has_t || stats, "nll_multi_fwd: targets need stats");
+  const dim3 grid((unsigned)((s_max + 255) / 256), (unsigned)k, (unsigned)v.a[0].n);
+  if (has_t)
+    hipLaunchKernelGGL(nll_multi_fwd_kernel<true>, grid, dim3(256), 0, ctx->stream, v, stats);
+  else
+    hipLaunchKernelGGL(nll_multi_fwd_kernel<false>, grid, dim3(256), 0, ctx->stream, v,
+                       (float*)nullptr);
+  E2_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int e2_nll_mix(e2_ctx* ctx, int k, const float* stats, const float* mixing_w,
+                          float* coef, float* term_loss, float* count, float* loss_out) {
+  E2_REQUIRE(ctx && stats && mixing_w && coef && term_loss && count && loss_out,
+             "nll_mix: null argument");
+  E2_REQUIRE(!ctx->loss_sum_mode, "nll_mix: not available in loss-gradient sum mode (one count "
+             "slot cannot hold the terms' counts)");
+  E2_REQUIRE(k >= 1 && k <= E2_MAX_LOSS_TERMS, "nll_mix: %d terms, 1..%d are supported", k,
+             E2_MAX_LOSS_TERMS);
+  hipLaunchKernelGGL(nll_mix_kernel, dim3(1), dim3(64), 0, ctx->stream, k, stats, mixing_w, coef,
+                     term_loss, count, loss_out);
+  E2_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int e2_nll_multi_bwd(e2_ctx* ctx, int k, const e2_tensor5* const* probs,
+                                const e2_tensor5* const* targets, const float* coef,
+                                const e2_tensor5* const* dlogits) {
+  NllMultiV v{};
+  bool has_t;
+  long s_max;
+  if (int rc = nll_multi_pack(ctx, "nll_multi_bwd", k, probs, "probs", targets, dlogits,
+                              "dlogits", true, &v, &has_t, &s_max))
+    return rc;
+  E2_REQUIRE(coef, "nll_multi_bwd: null coef");
+  const dim3 grid((unsigned)((s_max + 255) / 256), (unsigned)k, (unsigned)v.a[0].n);
+  hipLaunchKernelGGL(nll_multi_bwd_kernel, grid, dim3(256), 0, ctx->stream, v, coef);
   E2_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -1,15 +1,21 @@
 // body of softmax_nll_bwd_kernel / softmax_nll_bwd_w_kernel and of
-// softmax_nll_grouped_bwd_kernel (softmax_nll.hip): in scope are the flag WT, the kernel's
-// arguments and `NllW wt`.
+// softmax_nll_grouped_bwd_kernel / nll_multi_bwd_kernel (softmax_nll.hip): in scope are the flags
+// WT and COEF, the kernel's arguments and `NllW wt`.  COEF (e2_nll_multi_bwd): `stats` points at
+// the finished coefficient of this loss term -- nothing is normalised or reported here.
   const long S = (long)pr.d * pr.h * pr.w;
   const long s = blockIdx.x * 256L + threadIdx.x;
   const int n = blockIdx.z;
-  float inv = 1.f / (stats[1] + E2_EPS_NLL);
-  if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) {
-    if (loss_out) loss_out[0] = stats[0] * inv;
-    if (count_out) count_out[0] = stats[1];
+  float inv;
+  if constexpr (COEF) {
+    inv = stats[0];
+  } else {
+    inv = 1.f / (stats[1] + E2_EPS_NLL);
+    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) {
+      if (loss_out) loss_out[0] = stats[0] * inv;
+      if (count_out) count_out[0] = stats[1];
+    }
+    if (sum_mode) inv = 1.f;                // (e2_set_loss_grad_mode: unnormalised gradients)
   }
-  if (sum_mode) inv = 1.f;                  // (e2_set_loss_grad_mode: unnormalised gradients)
   if (s >= S) return;
   const int x = (int)(s % pr.w);
   const long t = s / pr.w;

@@ -2,7 +2,7 @@
 elektronn2/neuromancer (the subset on the 3-D conv/pool/upconv hot path)."""
 from .graphutils import TaggedShape, make_func, floatX, as_floatX
 from .variables import VariableParam, VariableWeight, ConstantParam, initweights
-from .node_basic import (Node, Input, Input_like, Concat, Add, model_manager,
+from .node_basic import (Node, Input, Input_like, split, SplitPart, Concat, Add, model_manager,
                          choose_name)
 from .neural import (Conv, UpConv, Pool, Crop, Pad, AutoMerge, UpConvMerge, FragmentsToDense, Perceptron,
                      LRN)

@@ -47,6 +47,19 @@ coefficients and the total; each term's backward launch writes (or adds to) its 
 gradient.  ``margin``, ``scale_correction`` and ``mixing_weights`` are non-trainable parameters the
 kernels read in place.  Mixing these with a MultinoulliNLL / MalisNLL raises NotImplementedError
 (their fused launches take no scale), and so does the ``'s'`` sample axis.
+
+Multi-task nets: ``AggregateLoss`` over 2..8 distinct ``MultinoulliNLL`` terms (sparse targets,
+``n_indep = 1``, unweighted), each over a ``Softmax`` of its own -- usually K ``(1,1,1)`` 'lin' heads
+on one trunk, the targets cut from one Input by ``node_basic.split`` -- is the form ``multi_nll``:
+    L_k = sum_labelled -log(p_target + 1e-5) / (N_k + 1e-5),   each term its OWN count N_k,
+    total = (1/K) sum_k w_k L_k;  a term with nothing labelled is 0, has a zero gradient, counts in K.
+The aggregate owns the launches: all heads, softmaxes, sums and gradients in one launch pair
+(csrc/multihead.hip; plan option ``fuse_multihead``, every head Conv of the classifier-head form on
+one trunk, sum of the classes <= 16) or, all-or-none, the heads as ordinary conv launches and the
+generic pair e2_nll_multi_fwd / e2_nll_multi_bwd over their logits (csrc/softmax_nll.hip); between
+them one small launch (e2_nll_mix) that reads ``mixing_weights`` on the device.  After a step each
+term's ``term_value`` / ``n_labelled`` hold its L_k and N_k.  Any other list that contains a
+MultinoulliNLL / MalisNLL raises as before.
 """
 from __future__ import annotations
 
@@ -95,6 +108,13 @@ class Softmax(Node):
         # probs only; when an NLL node hangs on this softmax it re-runs the same
         # kernel with the target and also fills the loss statistics.
         if plan.scratch.get((self, 'fused_nll')):
+            agg = self._multi_agg(plan)
+            if agg is not None and agg._last_softmax(plan) is self:
+                # several NLL terms under one aggregate: its forward launch writes every term's
+                # probabilities.  It is issued HERE, where the last of its softmaxes stands in
+                # the plan -- behind every head's logits, in front of every reader of the
+                # probabilities (a Concat prediction, Errors), whatever the order of the outputs
+                agg._emit_fwd(plan)
             return
         head = self._head(plan)
         if head is not None:                 # conv + softmax in one kernel
@@ -117,6 +137,15 @@ class Softmax(Node):
         p = self.parent
         f = getattr(p, '_fused_head', None)
         return p if (f is not None and f(plan) is self) else None
+
+    def _multi_agg(self, plan):
+        """the AggregateLoss of this plan that has a MultinoulliNLL over this softmax as one of
+        several terms -- its launches then make the probabilities, the loss and the gradient --
+        or None"""
+        for c in self.children.values():
+            if isinstance(c, MultinoulliNLL) and c._multi(plan) is not None:
+                return c._multi(plan)[0]
+        return None
 
     def _plan_bwd(self, plan):
         if plan.scratch.get((self, 'fused_nll')) or plan.scratch.get((self, 'loss_writes_dlogits')):
@@ -201,6 +230,43 @@ class MultinoulliNLL(Node):
         self.weakness = 0
         self.mask_class_labeled = mask_class_labeled
         self.mask_class_not_present = mask_class_not_present
+        self._last_plan = None
+
+    def _multi(self, plan):
+        """(aggregate, k): this node is term k of an ``AggregateLoss`` of the ``multi_nll`` form
+        that belongs to this plan -- the aggregate then owns every launch of the term -- else
+        None"""
+        key = (self, 'multi')
+        if key not in plan.scratch:
+            r = None
+            for c in self.children.values():
+                if getattr(c, 'multi_nll', False) and any(n is c for n in plan.nodes):
+                    r = (c, [i for i, p in enumerate(c.parent) if p is self][0])
+                    break
+            plan.scratch[key] = r
+        return plan.scratch[key]
+
+    def _mix_value(self, what):
+        plan = self._last_plan
+        agg = None if plan is None else plan.scratch.get((self, 'multi'))
+        if agg is None:
+            return None
+        plan.stream.synchronize()
+        return plan.scratch[agg[0], what][agg[1]].item()
+
+    @property
+    def term_value(self):
+        """as a term of a multi-NLL AggregateLoss: this term's L of the last step / evaluation,
+        before the mixing weight (None before the first, and for a single loss)"""
+        v = self._mix_value('term_loss')
+        return None if v is None else np.float32(v)
+
+    @property
+    def n_labelled(self):
+        """as a term of a multi-NLL AggregateLoss: labelled target positions of the last step /
+        evaluation (None before the first, and for a single loss)"""
+        v = self._mix_value('count')
+        return None if v is None else int(round(v))
 
     @property
     def weighted(self):
@@ -239,6 +305,9 @@ class MultinoulliNLL(Node):
 
     def _plan_alloc(self, plan):
         plan.scratch[self.pred, 'fused_nll'] = True
+        if self._multi(plan) is not None:     # (the aggregate allocates and launches)
+            plan.out[self] = None
+            return
         plan.scratch[self, 'loss'] = plan.zeros_flat(1)
         head = self.pred._head(plan)
         if head is not None and plan.training and self._tail(plan) is None:
@@ -258,6 +327,8 @@ class MultinoulliNLL(Node):
         return c if (t is not None and t[2] is self) else None
 
     def _plan_fwd(self, plan):
+        if self._multi(plan) is not None:
+            return
         stats = plan.scratch[self.pred, 'stats']
         tail = self._tail(plan)
         if tail is not None:
@@ -298,6 +369,8 @@ class MultinoulliNLL(Node):
                                  plan.out[self.pred], stats, weights=self._weights(plan))
 
     def _plan_bwd(self, plan):
+        if self._multi(plan) is not None:
+            return
         with plan.loss_grad_mode():
             self._plan_bwd_launches(plan)
 
@@ -643,10 +716,20 @@ class AggregateLoss(Node):
             raise ValueError("Unsupported weight format")
         self.params['mixing_weights'] = mixing_weights
         self.mixing_weights = mixing_weights
-        # two forms: exactly one MultinoulliNLL / MalisNLL (their own launches make the loss), or
-        # 1..MAX_LOSS_TERMS element-wise losses mixed by this node's launch (csrc/loss_elem.hip)
+        # three forms: exactly one MultinoulliNLL / MalisNLL (their own launches make the loss),
+        # 1..MAX_LOSS_TERMS element-wise losses mixed by this node's launch (csrc/loss_elem.hip),
+        # or 'multi_nll': 2..MAX_LOSS_TERMS distinct plain MultinoulliNLL terms, each over a
+        # softmax of its own, run and mixed by this node's launches (csrc/softmax_nll.hip)
         self.elementwise = len(parent_nodes) > 0 and \
             all(isinstance(n, _ElementLoss) for n in parent_nodes)
+        self.multi_nll = (
+            2 <= len(parent_nodes) <= MAX_LOSS_TERMS
+            and all(isinstance(n, MultinoulliNLL) and n.n_indep == 1 and not n.weighted
+                    for n in parent_nodes)
+            and len(set(id(n) for n in parent_nodes)) == len(parent_nodes)
+            and len(set(id(n.pred) for n in parent_nodes)) == len(parent_nodes))
+        if self.multi_nll:
+            return
         if self.elementwise:
             if len(parent_nodes) > MAX_LOSS_TERMS:
                 raise ValueError("AggregateLoss: %i losses given, the HIP hot path mixes at most %i"
@@ -666,8 +749,43 @@ class AggregateLoss(Node):
     def _calc_comp_cost(self):
         self.computational_cost = np.sum([inp.shape.stripnone_prod for inp in self.parent])
 
+    def _fused_heads(self, plan):
+        """multi_nll: the head Convs, in term order, when ALL terms run in the fused multi-head
+        launches (csrc/multihead.hip): plan option fuse_multihead, every term's logits from a
+        Conv of the classifier-head form (Conv._head_form), all of them on one trunk, within
+        e2_multihead_supported.  Else None: the generic pair reads materialised logits."""
+        key = (self, 'fused_heads')
+        if key not in plan.scratch:
+            heads = None
+            convs = [n.pred.parent for n in self.parent]
+            if (self.multi_nll and plan.opt['fuse_multihead']
+                    and all(getattr(c, '_head_form', None) is not None
+                            and c._head_form(plan) is n.pred for c, n in zip(convs, self.parent))
+                    and not isinstance(convs[0].parent, (list, tuple))
+                    and all(c.parent is convs[0].parent for c in convs)
+                    and plan.ctx.multihead_supported(convs[0].parent.shape['f'],
+                                                     [c.n_f for c in convs])):
+                heads = convs
+            plan.scratch[key] = heads
+        return plan.scratch[key]
+
     def _plan_alloc(self, plan):
         plan.out[self] = None
+        if self.multi_nll:
+            heads = self._fused_heads(plan)
+            if heads is not None and plan.training:
+                nb = plan.ctx.multihead_bwd_ws_bytes(plan.out_shape(heads[0].parent),
+                                                     sum(c.n_f for c in heads))
+                plan.scratch[self, 'head_ws'] = plan.empty_flat(nb // 4 + 16)
+            # one slab {S_0, N_0, S_1, N_1, ...}: every Softmax's 'stats' is its pair of it
+            K = len(self.parent)
+            slab = plan.zeros_flat(2 * K)
+            plan.scratch[self, 'stats'] = slab
+            for k, n in enumerate(self.parent):
+                plan.scratch[n.pred, 'stats'] = slab[2 * k:2 * k + 2]
+            for what in ('coef', 'term_loss', 'count'):
+                plan.scratch[self, what] = plan.zeros_flat(MAX_LOSS_TERMS)
+            plan.scratch[self, 'loss'] = plan.zeros_flat(1)
         if self.elementwise:
             for k, n in enumerate(self.parent):
                 plan.scratch[n, 'agg'] = (self, k)
@@ -676,8 +794,35 @@ class AggregateLoss(Node):
                 plan.scratch[self, what] = plan.zeros_flat(MAX_LOSS_TERMS)
             plan.scratch[self, 'loss'] = plan.zeros_flat(1)
 
+    def _last_softmax(self, plan):
+        """multi_nll: the term's Softmax that stands last in the plan's node order"""
+        preds = [n.pred for n in self.parent]
+        return max(preds, key=lambda sm: [i for i, n in enumerate(plan.nodes) if n is sm][0])
+
+    def _emit_fwd(self, plan):
+        """multi_nll: every term's probabilities and sums in one launch, then the mix (also in
+        forward-only plans: the total exists without a backward pass).  Issued by the last
+        Softmax of the terms (Softmax._plan_fwd), not at this node's own place in the plan."""
+        ps = list(self.parent)
+        slab = plan.scratch[self, 'stats']
+        plan.zero_early(slab)
+        heads = self._fused_heads(plan)
+        if heads is not None:          # trunk -> all logits -> softmaxes -> sums, one launch
+            plan.ctx.multihead_fwd(plan.out[heads[0].parent],
+                                   [plan.param(c.w).reshape(c.n_f, -1) for c in heads],
+                                   [plan.param(c.b) for c in heads],
+                                   [plan.out[n.target] for n in ps],
+                                   [plan.out[n.pred] for n in ps], slab)
+        else:
+            plan.ctx.nll_multi_fwd([plan.out[n.pred.parent] for n in ps],
+                                   [plan.out[n.target] for n in ps],
+                                   [plan.out[n.pred] for n in ps], slab)
+        plan.ctx.nll_mix(len(ps), slab, plan.param(self.mixing_weights).reshape(-1),
+                         plan.scratch[self, 'coef'], plan.scratch[self, 'term_loss'],
+                         plan.scratch[self, 'count'], plan.scratch[self, 'loss'])
+
     def _plan_fwd(self, plan):
-        if not self.elementwise:
+        if not self.elementwise:           # (multi_nll: _emit_fwd, issued by the last Softmax)
             return
         ps = list(self.parent)
         plan.ctx.loss_mix([n._term(plan) for n in ps], [plan.scratch[n, 'partials'] for n in ps],
@@ -687,19 +832,48 @@ class AggregateLoss(Node):
                           plan.scratch[self, 'loss'])
 
     def _plan_bwd(self, plan):
+        if self.multi_nll:
+            ps = list(self.parent)
+            heads = self._fused_heads(plan)
+            if heads is not None:
+                trunk = heads[0].parent
+                dst, first = (plan.grad_slot(trunk) if plan.needs_grad(trunk) else (None, True))
+                plan.ctx.multihead_bwd(plan.out[trunk],
+                                       [plan.param(c.w).reshape(c.n_f, -1) for c in heads],
+                                       [plan.out[n.pred] for n in ps],
+                                       [plan.out[n.target] for n in ps],
+                                       plan.scratch[self, 'coef'], dst, not first,
+                                       [plan.pgrad(c.w).reshape(c.n_f, -1) for c in heads],
+                                       [plan.pgrad(c.b) for c in heads],
+                                       plan.scratch[self, 'head_ws'])
+                return
+            dsts = []
+            for n in ps:
+                logits = n.pred.parent
+                if not plan.needs_grad(logits):
+                    raise NotImplementedError("AggregateLoss: term '%s' has no trainable "
+                                              "parameter upstream" % (n.name,))
+                dst, first = plan.grad_slot(logits)
+                if not first:
+                    raise NotImplementedError("logits consumed by several nodes")
+                dsts.append(dst)
+            plan.ctx.nll_multi_bwd([plan.out[n.pred] for n in ps],
+                                   [plan.out[n.target] for n in ps],
+                                   plan.scratch[self, 'coef'], dsts)
+            return
         pass          # d(total)/d(nll) = mixing_weight(=1) / 1 ; folded into the NLL backward
                       # (element-wise losses: coef[k], which each term's backward launch reads)
 
     def loss_dev(self, plan):
         """the one-element device tensor that holds the step's loss"""
-        if self.elementwise:
+        if self.elementwise or self.multi_nll:
             for n in self.parent:
                 n._last_plan = plan
             return plan.scratch[self, 'loss']
         return plan.scratch[self.parent[0], 'loss']
 
     def host_value(self, plan):
-        if self.elementwise:
+        if self.elementwise or self.multi_nll:
             return np.float32(self.loss_dev(plan).item())
         w = float(self.mixing_weights.get_value()[0])
         return np.float32(float(self.parent[0].loss_value(plan).item()) * w)

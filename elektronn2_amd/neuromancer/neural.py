@@ -497,11 +497,11 @@ class Conv(NeuralLayer):
     def _mfp_pool(self):
         return bool(self.mfp) and not all(p == 1 for p in self._p3)
 
-    def _fused_head(self, plan):
-        """classifier head: this (1,1,1) 'lin' conv to <= 4 features feeds nothing but a
-        Softmax of the same plan -> conv + softmax (+ NLL and all gradients) run in the
-        fused head kernels (csrc/head.hip); returns that Softmax node or None."""
-        key = (self, 'head')
+    def _head_form(self, plan):
+        """this (1,1,1) 'lin' conv feeds nothing but a Softmax of the same plan and has nothing
+        that needs its logits in memory: the form of a classifier head, whatever the fused
+        kernels' size limits; returns that Softmax node or None."""
+        key = (self, 'head_form')
         if key not in plan.scratch:
             sm = None
             kids = list(self.children.values())
@@ -512,9 +512,30 @@ class Conv(NeuralLayer):
                     and kids[0].n_indep == 1
                     and any(n is kids[0] for n in plan.nodes)
                     and not any(n is self for n in plan.outputs)
-                    and plan.ctx.head_supported(self.parent.shape['f'], self.n_f)
                     and not self._fused_first(plan)):
                 sm = kids[0]
+            plan.scratch[key] = sm
+        return plan.scratch[key]
+
+    def _fused_head(self, plan):
+        """classifier head: this (1,1,1) 'lin' conv to <= 4 features feeds nothing but a
+        Softmax of the same plan -> conv + softmax (+ NLL and all gradients) run in the
+        fused head kernels (csrc/head.hip); returns that Softmax node or None.  Where the
+        softmax's NLL is one of several terms of an AggregateLoss of this plan, the answer is the
+        aggregate's: all of its heads in the fused multi-head launches (csrc/multihead.hip; the
+        Softmax is returned, this node issues nothing) or none of them (None: the logits are
+        made by the ordinary 'lin' launches and read by the aggregate's generic pair)."""
+        key = (self, 'head')
+        if key not in plan.scratch:
+            sm = self._head_form(plan)
+            if sm is not None:
+                agg = sm._multi_agg(plan)
+                if agg is not None:
+                    heads = agg._fused_heads(plan)
+                    if heads is None or not any(h is self for h in heads):
+                        sm = None
+                elif not plan.ctx.head_supported(self.parent.shape['f'], self.n_f):
+                    sm = None
             plan.scratch[key] = sm
         return plan.scratch[key]
 

@@ -5,7 +5,9 @@ Mirrors elektronn2/neuromancer/node_basic.py: ``ModelContainer`` /
 registration of every node in the current model (``MetaNode`` :200-302),
 ``Node`` (:307-574 -- ``_make_output/_calc_shape/_calc_comp_cost``, ``params``,
 ``shape``, callable on numpy arrays), ``Input`` (:1182-1243), ``Input_like``
-(:1246-1271), ``Concat`` (:1403-1451), ``Add`` (:1455-1483).
+(:1246-1271), ``split`` (:1335-1398; along ``'f'``, each part a ``SplitPart`` view: how one
+target Input with several features feeds several losses), ``Concat`` (:1403-1451), ``Add``
+(:1455-1483).
 
 There is no symbolic tensor engine here: ``node.output`` is a small ``Sym``
 handle (dtype + owner) and the numerics run through a static launch plan
@@ -30,7 +32,7 @@ from .graphutils import TaggedShape, floatX
 
 logger = logging.getLogger('elektronn2log')
 
-__all__ = ['Node', 'Input', 'Input_like', 'Concat', 'Add', 'model_manager',
+__all__ = ['Node', 'Input', 'Input_like', 'split', 'SplitPart', 'Concat', 'Add', 'model_manager',
            'choose_name', 'Sym']
 
 
@@ -575,6 +577,89 @@ def Input_like(ref, dtype=None, name='input', print_repr=True, override_f=False,
                                        override_f=override_f,
                                        hardcoded_shape=hardcoded_shape))
     return node
+
+
+class SplitPart(Node):
+    """One part of ``split``: features ``lo:hi`` of its parent, a zero-copy channel-slice view of
+    the parent's output -- no launch, no source node (the unsplit parent stays the model's
+    input).  A node class of its own so that ``Model.save`` / ``modelload`` describe and rebuild
+    the parts like every other node."""
+
+    def __init__(self, parent, lo, hi, name="split", print_repr=False):
+        super(SplitPart, self).__init__(parent, name, print_repr)
+        n_f = parent.shape['f']
+        self.lo, self.hi = int(lo), int(hi)
+        if not 0 <= self.lo < self.hi <= n_f:
+            raise ValueError("SplitPart: features %i:%i of %s" % (self.lo, self.hi, parent.shape))
+
+    def _calc_shape(self):
+        self.shape = self.parent.shape.updateshape(self.parent.shape.tag2index('f'),
+                                                   self.hi - self.lo)
+
+    def _calc_comp_cost(self):
+        self.computational_cost = 0
+
+    def _plan_alloc(self, plan):
+        if plan.needs_grad(self):
+            raise NotImplementedError(
+                "split: part '%s' needs a gradient (trainable parameters upstream of '%s', on the "
+                "loss path); the HIP hot path splits targets and other inputs only"
+                % (self.name, self.parent.name))
+        src = plan.out.get(self.parent)
+        if src is None:
+            raise NotImplementedError("split: the output of '%s' is not materialised by the plan"
+                                      % (self.parent.name,))
+        plan.out[self] = src[:, self.lo:self.hi]
+
+    def _plan_fwd(self, plan):
+        pass
+
+    def _plan_bwd(self, plan):
+        pass
+
+
+def split(node, axis='f', index=None, n_out=None, strip_singleton_dims=False, name='split'):
+    """node_basic.py:1335-1398: cut ``node`` along ``axis`` into ``n_out`` equal parts, or at the
+    positions ``index``; returns a tuple of nodes.  ``name``: one name (made unique per part) or a
+    list with one name per part.  The HIP hot path splits along ``'f'`` only, each part a view
+    (``SplitPart``); ``strip_singleton_dims`` and parts that need a gradient raise
+    NotImplementedError."""
+    shape = node.shape
+    tags = list(shape.tags)
+    if isinstance(axis, str):
+        if axis not in tags:
+            raise ValueError("split: shape %s has no axis %r" % (shape, axis))
+        ax = tags.index(axis)
+    else:
+        ax = int(axis)
+        if not -len(tags) <= ax < len(tags):
+            raise ValueError("split: shape %s has no axis %r" % (shape, axis))
+        ax %= len(tags)
+    size = shape.shape[ax]
+    if index is None and n_out is None:
+        raise ValueError("split needs index or n_out")
+    if index is not None:
+        cuts = np.atleast_1d(np.asarray(index, dtype=np.int64))
+        if size is not None and cuts.size and cuts.max() >= size:
+            raise ValueError("split: index %s reaches past axis %r of %s (size %s)"
+                             % (cuts.tolist(), axis, shape, size))
+    else:
+        step, rest = divmod(size, int(n_out))
+        if rest:
+            raise ValueError("split: %i parts do not divide axis %r of size %i" % (n_out, axis, size))
+        cuts = step * np.arange(1, int(n_out))
+    if tags[ax] != 'f':
+        raise NotImplementedError("split along axis %r: the HIP hot path splits the feature axis "
+                                  "'f' only (a part is a channel-slice view)" % (axis,))
+    if strip_singleton_dims:
+        raise NotImplementedError("split(strip_singleton_dims=True): every node of the HIP hot "
+                                  "path keeps its 'f' axis")
+    bounds = np.concatenate([[0], cuts, [size]]).astype(int)
+    ranges = list(zip(bounds[:-1].tolist(), bounds[1:].tolist()))
+    names = list(name) if isinstance(name, (list, tuple)) else [name] * len(ranges)
+    if len(names) != len(ranges):
+        raise ValueError("split: %i names for %i parts" % (len(names), len(ranges)))
+    return tuple(SplitPart(node, lo, hi, name=nme) for (lo, hi), nme in zip(ranges, names))
 
 
 class Concat(Node):

@@ -53,6 +53,11 @@ SPEC = {
     "side_pack": ("E2_SIDE_PACK", _b, False, "weight repack as a parallel branch (measured slower)"),
     "fuse_actbwd": ("E2_FUSE_ACTBWD", int, 0, "relu backward in the consumer's dgrad epilogue (finding 17)"),
     "fuse_tail": ("E2_FUSE_TAIL", _b, True, "last 1x1x1 conv + head + loss in one launch (finding 33)"),
+    "fuse_multihead": ("E2_FUSE_MULTIHEAD", _b, True,
+                       "several MultinoulliNLL terms under one AggregateLoss whose softmaxes sit on (1,1,1) "
+                       "'lin' convs of one trunk: all heads, their softmaxes, losses and gradients in one "
+                       "launch pair (csrc/multihead.hip); off: the heads run as ordinary conv launches and the "
+                       "generic pair of csrc/softmax_nll.hip reads their logits"),
     "bf16_tail": ("E2_BF16_TAIL", _b, True,
                   "bf16 mode: the tail launch too (its two GEMMs round their operands in registers)"),
     "tail_gm": ("E2_TAIL_GM", _b, True, "the tail launch carries its parent's activation backward"),

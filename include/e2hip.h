@@ -546,6 +546,73 @@ int e2_softmax_nll_grouped_bwd(e2_ctx*, const e2_tensor5* probs, const e2_tensor
                                int n_indep, const float* stats, const e2_tensor5* dlogits,
                                float* loss_out);
 
+/* ---- K MultinoulliNLL terms under one AggregateLoss ("multi-target training": one trunk, K
+ *      softmax heads, loss.py:261-347 per term, 1357-1363 for the mix), 1 <= K <=
+ *      E2_MAX_LOSS_TERMS.  Term j has c_j classes, n_indep = 1, logits / probs / dlogits
+ *      (n, c_j, spatial_j) and a sparse target (n, 1, spatial_j) of float class ids; the terms
+ *      share the batch size and may differ in class count and spatial size.  With
+ *        T = 1 where the id equals an integer in [0, c_j), else 0 (negative, >= c_j and
+ *            non-integer ids are unlabelled)
+ *        S_j = sum_{T=1} -log(p_target + 1e-5)    N_j = sum T    L_j = S_j / (N_j + 1e-5)
+ *        total  = (1/K) sum_j w_j L_j             (w = mixing_w)
+ *        coef_j = w_j / (K (N_j + 1e-5))
+ *        dlogits_j[c] = T coef_j (-p_t / (p_t + 1e-5)) ([c == target] - p_c)
+ *      Every term has its OWN normaliser (the groups of e2_softmax_nll_grouped_* share one).  A
+ *      term with nothing labelled has L_j = 0 and a gradient of exact zeros and still counts in K;
+ *      nothing labelled anywhere: total 0, every gradient 0.
+ *      e2_nll_multi_fwd: ONE launch for all terms; writes probs_j and ADDS to stats = 2K device
+ *      floats {S_0, N_0, S_1, N_1, ...} (zeroed by the caller).  targets NULL, or all its entries
+ *      NULL: probabilities only, stats is untouched and may be NULL.  The probabilities are bit-
+ *      equal to e2_softmax_nll_fwd's.
+ *      e2_nll_mix: one small launch; writes coef[j], term_loss[j] = L_j, count[j] = N_j (K floats
+ *      each) and loss_out[0] = total.  mixing_w is DEVICE memory read when the kernel runs: a
+ *      captured launch follows its contents.
+ *      e2_nll_multi_bwd: ONE launch; dlogits_j may alias probs_j.
+ *      logits / targets / probs / dlogits are HOST arrays of K view pointers (the views go by value
+ *      into the kernel arguments); every view may be strided (channel slices of wider buffers),
+ *      nothing outside the output views is written.  Errors, nothing launched: K out of range,
+ *      NULL arguments, some but not all targets NULL, class / batch / spatial extents that
+ *      disagree, and every call while e2_set_loss_grad_mode has sum mode on (its one count slot
+ *      cannot hold K counts). ------------------------------------------------------------------ */
+int e2_nll_multi_fwd(e2_ctx*, int k, const e2_tensor5* const* logits,
+                     const e2_tensor5* const* targets, const e2_tensor5* const* probs,
+                     float* stats);
+int e2_nll_mix(e2_ctx*, int k, const float* stats, const float* mixing_w, float* coef,
+               float* term_loss, float* count, float* loss_out);
+int e2_nll_multi_bwd(e2_ctx*, int k, const e2_tensor5* const* probs,
+                     const e2_tensor5* const* targets, const float* coef,
+                     const e2_tensor5* const* dlogits);
+
+/* ---- the same K terms where every softmax sits on a 1x1x1 'lin' conv of ONE trunk x
+ *      (n, cin, d, h, w): K classifier heads fused (csrc/multihead.hip).  Head j: w_j the dense
+ *      (ncls_j, cin) weights and bias_j[ncls_j] of its own parameter, probs_j (n, ncls_j, d, h, w),
+ *      target_j (n, 1, d, h, w).  Supported: 2 <= k <= 8, every ncls_j >= 2, sum ncls_j <= 16,
+ *      1 <= cin <= 512.
+ *      e2_multihead_fwd: one launch; every element of x is read once, all sum ncls logits
+ *      z_j = W_j x + b_j are formed, one softmax per head goes to probs_j, and with targets
+ *      stats[2j] += S_j, stats[2j+1] += N_j as e2_nll_multi_fwd (zero stats first).  targets
+ *      NULL, or all its entries NULL: probabilities only, stats untouched (may be NULL).
+ *      e2_multihead_bwd: with dlogits_j as above from probs_j, target_j and coef[j] (device, from
+ *      e2_nll_mix): dx = sum_j W_j^T dlogits_j written once (accumulate_dx != 0: added; dx NULL:
+ *      not wanted), dw_j[ncls_j*cin] and dbias_j[ncls_j] ACCUMULATED (zero them first) through
+ *      per-work-group partial sums in ws and a reduce launch.  ws:
+ *      e2_multihead_bwd_workspace_bytes(n, cin, sum ncls, d, h, w) bytes.
+ *      w / bias / ncls / targets / probs / dw / dbias are HOST arrays of k entries; all views may
+ *      be strided (x a channel slice, probs_j slices of one concat buffer, targets channels of one
+ *      buffer).  f32 arithmetic in either mfma mode.  Errors, nothing launched: an unsupported
+ *      case, NULL arguments, some but not all targets NULL, class / batch / spatial mismatches, a
+ *      short workspace, and every call while e2_set_loss_grad_mode has sum mode on. ------------ */
+int e2_multihead_supported(int cin, int k, const int* ncls);
+int e2_multihead_fwd(e2_ctx*, const e2_tensor5* x, int k, const float* const* w,
+                     const float* const* bias, const int* ncls,
+                     const e2_tensor5* const* targets, const e2_tensor5* const* probs,
+                     float* stats);
+size_t e2_multihead_bwd_workspace_bytes(int n, int cin, int sum_ncls, int d, int h, int w);
+int e2_multihead_bwd(e2_ctx*, const e2_tensor5* x, int k, const float* const* w,
+                     const e2_tensor5* const* probs, const e2_tensor5* const* targets,
+                     const float* coef, const e2_tensor5* dx, int accumulate_dx,
+                     float* const* dw, float* const* dbias, void* ws, size_t ws_bytes);
+
 /* ---- weighted MultinoulliNLL: class / example weights and the lazy-labelling masks
  *      (loss.py:172-212 arguments, loss.py:261-347 computation; n_indep = 1, sparse targets,
  *      weakness = 0).  With t = target class id (< 0: unlabelled), w = class_w, e = example_w,
