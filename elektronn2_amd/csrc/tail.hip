@@ -195,8 +195,9 @@ __global__ __launch_bounds__(256) void tail_count_w_kernel(const float* tg, long
 }
 
 // slot sums -> dwh / dbh / db1 (ADDED: the gradient arena was zeroed), stats[0] and the loss.
-// One wave per element: its slots are contiguous, the sum has ONE writer (no atomics, a fixed
-// summation order).  (The first cut walked the slots with one thread per element: 214
+// One wave per element: its slots are contiguous, the sum has ONE writer (a fixed summation
+// order); it is ADDED with an atomic, because a bias that the layer shares with its parent (or the
+// head) makes two elements' destinations one address.  (The first cut walked the slots with one thread per element: 214
 // dependent-latency loads for the loss alone, 46 us.)
 __global__ __launch_bounds__(256) void tail_reduce_kernel(const float* __restrict__ part, int nWG,
                                                           int nc, int c2, float* dwh, float* dbh,
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(256) void tail_reduce_kernel(const float* __restric
   float* dst = idx < nc * c2 ? dwh + idx
              : (idx < nc * c2 + nc ? dbh + (idx - nc * c2)
              : (idx < nc * c2 + nc + c2 ? db1 + (idx - nc * c2 - nc) : dbp + (idx - nc * c2 - nc - c2 - 1)));
-  *dst += s;
+  unsafeAtomicAdd(dst, s);
 }
 
 // dense in (z, y, x): a position is one flat index

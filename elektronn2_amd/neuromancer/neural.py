@@ -1058,8 +1058,18 @@ class Conv(NeuralLayer):
         def wgrad_launch():
             ctx.set_input_slack(slack)
             try:
+                once = None
+                if plan.shared(self.w) and not plan._capturing and autotune.enabled() \
+                        and autotune.known(ctx, 'wgrad', sig) is None:
+                    # the tuner's overwriting runs would wipe what another node has added to the
+                    # shared slot: put that back, then ADD this node's gradient once
+                    keep = dw.clone()
+
+                    def once():
+                        dw.copy_(keep)
+                        wgrad(True)
                 plan.tuned('wgrad', sig, self._candidates(plan, 'wgrad'),
-                           lambda: wgrad(True), fn_tune=lambda: wgrad(False))
+                           lambda: wgrad(True), fn_tune=lambda: wgrad(False), fn_once=once)
             finally:
                 ctx.set_input_slack(0)
         plan.on_side(wgrad_launch, defer=True, force=plan.side_forced(self))
@@ -1377,6 +1387,10 @@ class UpConv(Conv):
         cin = self.parent.shape['f']
         nb = plan.ctx.upconv_ws_bytes(self.n_f, cin, self.pool_shape, xs)
         plan.scratch[self, 'ws'] = plan.empty_flat(nb // 4 + 64)
+        if plan.training and (plan.shared(self.w) or plan.shared(self.b)):
+            # (UpConv._plan_bwd: this node's own contribution to a shared parameter's gradient)
+            plan.scratch[self, 'dw_own'] = plan.empty_flat(int(np.prod(self.w_sh)))
+            plan.scratch[self, 'db_own'] = plan.empty_flat(self.n_f)
         # the two packed images, refreshed by the plan's one repack launch per step (they
         # used to be repacked inside every forward and backward call: two launches per node)
         w5 = plan._w5(plan.param(self.w))
@@ -1459,19 +1473,32 @@ class UpConv(Conv):
                                   plan.scratch[self, 'dlin'],
                                   plan.pgrad(self.gamma) if self.gamma.apply_train else None, dbias)
             dout, act, dbias = plan.scratch[self, 'dlin'], 'lin', None
+        # a parameter shared with another node: its slot may hold that node's contribution, which
+        # an overwriting call would wipe -- this node's goes to buffers of its own (overwritten:
+        # still idempotent) and is added to the slots behind the tuner
+        dw, own = plan.pgrad(self.w), []
+        if (self, 'dw_own') in plan.scratch and not (packed and plan._capturing):
+            if plan.shared(self.w):
+                own.append((plan.scratch[self, 'dw_own'], dw))
+                dw = own[-1][0]
+            if dbias is not None and plan.shared(self.b):
+                own.append((plan.scratch[self, 'db_own'], dbias))
+                dbias = own[-1][0]
 
         def run():
             if packed:
                 ctx.upconv3d_bwd_packed(plan.out[self.parent], wp_d, plan.out[self],
                                         dout, self.pool_shape, act,
-                                        dx, plan.pgrad(self.w), dbias,
+                                        dx, dw, dbias,
                                         plan.scratch[self, 'ws'], accumulate=plan._capturing)
             else:
                 ctx.upconv3d_bwd(plan.out[self.parent], plan.param(self.w), plan.out[self],
                                  dout, self.pool_shape, act, dx,
-                                 plan.pgrad(self.w), dbias, plan.scratch[self, 'ws'])
+                                 dw, dbias, plan.scratch[self, 'ws'])
         plan.tuned('igemm', sigs['dgrad'][0], sigs['dgrad'][1] if dx is not None else [],
                    lambda: plan.tuned('wgrad', sigs['wgrad'][0], sigs['wgrad'][1], run))
+        for src, slot in own:
+            ctx.copy5(src.reshape(1, 1, 1, 1, -1), slot.reshape(1, 1, 1, 1, -1), accumulate=True)
         if dx is not None and not first:
             ctx.copy5(dx, dst, accumulate=True)
 

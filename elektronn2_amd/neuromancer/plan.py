@@ -91,6 +91,19 @@ class Plan(object):
         # issues the tick and the gate launches
         self._drop_nodes = [n for n in self.nodes if getattr(n, 'dropout_rate', None) is not None]
         self._drop_ids = set(id(n) for n in self._drop_nodes)
+        # parameters that more than one node of this plan reads (w=<other>.w, ...): their gradient
+        # slot receives several contributions per step ("Shared parameters")
+        users = {}
+        for n in self.nodes:
+            for key in ('w', 'b', 'gamma'):
+                p = getattr(n, key, None)
+                if p is not None and hasattr(p, 'get_value'):
+                    users.setdefault(id(p), set()).add(id(n))
+        self._shared_ids = set(k for k, v in users.items() if len(v) > 1)
+
+    def shared(self, p):
+        """is parameter ``p`` read by several nodes of this plan?"""
+        return id(p) in self._shared_ids
 
     # ---- allocation helpers ---------------------------------------------------
     SLACK = 32       # floats of ZEROED slack behind every tensor of the plan (e2_set_input_slack)
@@ -612,6 +625,9 @@ class Plan(object):
                         return                       # (a frozen conv weight: keep the two launches)
                     by_param[id(w)] = [w, tuple(int(v) for v in w5.shape), None, None]
                     order.append(id(w))
+                if by_param[id(w)][2 + mode] is not None:
+                    return                           # (a shared weight: every node owns its images, the
+                                                     # update job holds one pair -- keep the two launches)
                 by_param[id(w)][2 + mode] = wp
             else:
                 up.append((w5, wp, mode))
