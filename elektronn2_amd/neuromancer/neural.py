@@ -1108,6 +1108,7 @@ class Conv(NeuralLayer):
         # parent's slabs, its activation backward adds them up
         gparts = plan.scratch.get((self.parent, 'grad_parts')) if first else None
         got = [1]
+        atomics = [False]                  # the (last) launch added onto a zero fill of `out`
         dyi = self._dy_inset(plan)         # ('same' / 'full': the interior's gradient only)
         zin = self._q3[0]
 
@@ -1132,19 +1133,29 @@ class Conv(NeuralLayer):
                     self._need_f32_dy(plan)
                     ctx.conv3d_dgrad_bf16(dyi, self._w5(plan.param(self.w)), out,
                                           ws=plan.bf16_ws(self))
-                got[0] = 1
+                got[0], atomics[0] = 1, False
             elif gparts is not None:
                 self._need_f32_dy(plan)
                 with plan.image(wp):
                     got[0] = ctx.conv3d_dgrad_packed_parts(dyi, wp, cin, self._k3, gparts)
+                atomics[0] = False
             else:
                 self._need_f32_dy(plan)
                 with plan.image(wp):
                     ctx.conv3d_dgrad_packed(dyi, wp, cin, self._k3, out)
-        plan.tuned('igemm', self._sig_dgrad(plan), self._candidates(plan, 'dgrad'), dgrad, out=out)
+                ptr, n = ctx.conv_last_zero_fill()
+                atomics[0] = bool(n) and ptr == out.data_ptr()
+        # a later writer's scratch tensor is shared (Plan.tmp_like: one per shape) with the other
+        # later writers of the step, which overwrite it or fill it for themselves: a split-K launch
+        # into it keeps its own zero fill in line -- the captured step's one fill at the head of
+        # the segment (Plan.tuned, `out`) would run in front of ALL of them
+        plan.tuned('igemm', self._sig_dgrad(plan), self._candidates(plan, 'dgrad'), dgrad,
+                   out=out if first else None)
         if first:
             plan.scratch[self.parent, 'grad_nparts'] = got[0]
         if not first:
+            # (for the record: did this later writer split K, i.e. fill the scratch tensor itself?)
+            plan.scratch[self, 'dgrad_atomics'] = atomics[0]
             ctx.copy5(out, dst, accumulate=True)
 
     def _actbwd_into_parent(self, plan):
