@@ -148,6 +148,11 @@ def _load():
         "e2_warp_slice": (C.c_int, [vp, P5, C.POINTER(C.c_float), i, C.c_uint,
                                     C.POINTER(C.c_int), C.POINTER(C.c_float), P5]),
         "e2_grey_augment": (C.c_int, [vp, fp, C.c_size_t, C.c_float, C.c_float, C.c_float]),
+        "e2_target_stride": (C.c_int, [vp, P5, C.POINTER(C.c_int), P5]),
+        "e2_target_nhood": (C.c_int, [vp, P5, C.POINTER(C.c_int), i, C.POINTER(C.c_int), P5]),
+        "e2_target_affinity": (C.c_int, [vp, P5, C.POINTER(C.c_int), i, C.POINTER(C.c_int), P5]),
+        "e2_count_negative": (C.c_int, [vp, P5, C.c_void_p]),
+        "e2_ids2barriers": (C.c_int, [vp, P5, C.POINTER(C.c_int), C.POINTER(C.c_int), i, P5]),
         "e2_stream_fork": (C.c_int, [vp, C.c_void_p]),
         "e2_stream_join": (C.c_int, [vp, C.c_void_p]),
         "e2_conv1_supported": (C.c_int, [i, i, i, i, i, i, i]),
@@ -495,6 +500,53 @@ class Context:
             raise TypeError("grey_augment needs a dense channel")
         _chk(_lib.e2_grey_augment(self.h, _fp(chan), chan.numel(), float(alpha), float(c),
                                   float(gamma)), "e2_grey_augment")
+
+    # ---- target forms of the batch creator (targets.hip) --------------------------
+    @staticmethod
+    def _ints3(v):
+        v = [int(x) for x in v]
+        if len(v) != 3:
+            raise ValueError("expected three values, got %r" % (v,))
+        return (C.c_int * 3)(*v)
+
+    @staticmethod
+    def _nhood(nhood):
+        nh = np.ascontiguousarray(nhood, np.int32)
+        if nh.ndim != 2 or nh.shape[1] != 3:
+            raise ValueError("nhood must be (E, 3), got %s" % (nh.shape,))
+        return (C.c_int * nh.size)(*[int(v) for v in nh.ravel()]), int(nh.shape[0])
+
+    def target_stride(self, t, stride, dst):
+        """dst (n, C, d, h, w) = t[..., ::sz, ::sx, ::sy] with NaN -> -666"""
+        _chk(_lib.e2_target_stride(self.h, C.byref(t5(t)), self._ints3(stride), C.byref(t5(dst))),
+             "e2_target_stride")
+
+    def target_nhood(self, t, nhood, stride, dst):
+        """dst (n, E + C - 1, d, h, w): channel 0 of t shifted by every row of ``nhood`` (-1 where
+        the shift leaves the patch), then the stride; the other channels strided; NaN -> -666"""
+        nh, E = self._nhood(nhood)
+        _chk(_lib.e2_target_nhood(self.h, C.byref(t5(t)), nh, E, self._ints3(stride),
+                                  C.byref(t5(dst))), "e2_target_nhood")
+
+    def target_affinity(self, t, nhood, stride, dst):
+        """dst (n, E, d, h, w) = the affinity graph (0 / 1) of the rounded, strided channel 0 of t"""
+        nh, E = self._nhood(nhood)
+        _chk(_lib.e2_target_affinity(self.h, C.byref(t5(t)), nh, E, self._ints3(stride),
+                                     C.byref(t5(dst))), "e2_target_affinity")
+
+    def count_negative(self, t, count):
+        """count[0] += #{t < 0}; ``count``: a one-element int32 device tensor the caller zeroes"""
+        if count.dtype != torch.int32 or not count.is_cuda or count.numel() < 1:
+            raise TypeError("count_negative: count must be an int32 GPU tensor")
+        _chk(_lib.e2_count_negative(self.h, C.byref(t5(t)), C.c_void_p(count.data_ptr())),
+             "e2_count_negative")
+
+    def ids2barriers(self, ids, dilute, connectivity, ecs_mode, dst):
+        """ids, dst (1, 1, D, H, W); ecs_mode 0 none, 1 ECS (id 0) is barrier, 2 ECS a class of its own"""
+        _chk(_lib.e2_ids2barriers(self.h, C.byref(t5(ids)),
+                                  self._ints3([bool(v) for v in dilute]),
+                                  self._ints3([bool(v) for v in connectivity]), int(ecs_mode),
+                                  C.byref(t5(dst))), "e2_ids2barriers")
 
     # ---- fused classifier head -------------------------------------------------
     @staticmethod

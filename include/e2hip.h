@@ -785,6 +785,36 @@ int e2_warp_slice(e2_ctx*, const e2_tensor5* src, const float* minv, int perspec
 /* d = clip(d * alpha + c, 0, 1) ** gamma on one dense channel of n floats, in place */
 int e2_grey_augment(e2_ctx*, float* d, size_t n, float alpha, float c, float gamma);
 
+/* ---- target forms of the batch creator, on the device (targets.hip; data/cnndata.py:319-396,
+ *      data/image.py:80-102, :138-220).  t = full-resolution target patches (n, C, D, H, W);
+ *      stride = (sz, sx, sy) >= 1 and nhood = E x 3 displacements (E <= 64) in HOST memory;
+ *      ts[n,c,z,x,y] = t[n,c,z sz,x sx,y sy] with extents ceil(D/sz), ...; all views arbitrary
+ *      (unit w stride), nothing outside them is read or written; one launch each.
+ * e2_target_stride:   dst (n, C, d, h, w) = ts, NaN -> -666.
+ * e2_target_nhood:    dst (n, E + C - 1, d, h, w): channel e < E = t[n, 0, p s - nhood[e]], -1 where
+ *                     that lies outside (D, H, W) (the shift acts on the full-resolution patch, then
+ *                     the stride); channels E.. = ts[:, 1:]; NaN -> -666.  |nhood[e][k]| must be
+ *                     smaller than the extent of axis k.
+ * e2_target_affinity: dst (n, E, d, h, w) = 1 where p + nhood[e] lies inside (d, h, w) and
+ *                     a = rint(ts[n,0,p]), b = rint(ts[n,0,p + nhood[e]]) are equal and both > 0,
+ *                     else 0 (NaN, zero and negative ids connect to nothing):
+ *                     malis.seg_to_affgraph of the rounded strided ids.
+ * e2_count_negative:  count[0] += #{t < 0} over the view (NaN is not negative); count: one
+ *                     unsigned in DEVICE memory that the caller zeroes; integer atomics.
+ * e2_ids2barriers:    ids, dst (1, 1, D, H, W): the 0 / 1 (/ 2) barrier volume of ids2barriers with
+ *                     smoothen=False -- the reference's forward pass and its pass over the reversed
+ *                     volume, edge behaviour included -- written as a gather (no atomics, bit-
+ *                     reproducible).  dilute / connectivity: 3 ints each in HOST memory; ecs_mode:
+ *                     0 none, 1 max(ids == 0, barriers), 2 'new_class' (ids == 0 and no barrier -> 2). */
+int e2_target_stride(e2_ctx*, const e2_tensor5* t, const int* stride, const e2_tensor5* dst);
+int e2_target_nhood(e2_ctx*, const e2_tensor5* t, const int* nhood, int E, const int* stride,
+                    const e2_tensor5* dst);
+int e2_target_affinity(e2_ctx*, const e2_tensor5* t, const int* nhood, int E, const int* stride,
+                       const e2_tensor5* dst);
+int e2_count_negative(e2_ctx*, const e2_tensor5* t, unsigned* count);
+int e2_ids2barriers(e2_ctx*, const e2_tensor5* ids, const int* dilute, const int* connectivity,
+                    int ecs_mode, const e2_tensor5* dst);
+
 /* ---- MALIS (host code, no GPU involved; malis/_malis_lib.cpp:38-167 via
  *      malis/_malis.pyx:42-123).  e2_malis_loss_weights: counts[e] = number of voxel
  *      pairs whose maximin edge in the affinity graph is e and whose ground-truth ids are
