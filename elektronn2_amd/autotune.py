@@ -254,7 +254,26 @@ def wgrad_candidates(cout, cin, k, out_sp, n_cu=256):
                             cands.append("%d,%d,%d,%d,%d" % (mt, nt, wk + 100, bp, q))
     return sorted(set(cands) | set(pointwise_wgrad_candidates(cout, cin, k, out_sp, n_cu))
                   | set(position_split_wgrad_candidates(cout, cin, k, out_sp, n_cu))
-                  | set(even_split_wgrad_candidates(cout, cin, k, out_sp, n_cu)))
+                  | set(even_split_wgrad_candidates(cout, cin, k, out_sp, n_cu))
+                  | set(six_product_wgrad_candidates(cout, cin, k, out_sp, n_cu)))
+
+
+def six_product_form(c):
+    """the "MT,NT,18,..." / "MT,NT,19,..." string of an 8 / 9 tiling -- the same kernel with every
+    f32 product made of six bf16 MFMA products (csrc/conv_pw_wgrad.hip) -- else None"""
+    v = c.split(",")
+    if len(v) == 5 and v[2] in ("8", "9"):
+        return ",".join(v[:2] + ["1" + v[2]] + v[3:])
+    return None
+
+
+def six_product_wgrad_candidates(cout, cin, k, out_sp, n_cu=256):
+    """every 8 / 9 candidate of the three generators below in its six-product form (a list of its
+    own: theirs hold one form each, which tests/test_host_logic.py pins)"""
+    out = []
+    for gen in (pointwise_wgrad_candidates, position_split_wgrad_candidates, even_split_wgrad_candidates):
+        out += [six_product_form(c) for c in gen(cout, cin, k, out_sp, n_cu)]
+    return sorted(set(c for c in out if c))
 
 
 WGRAD_KS_TILES = [(13, 2), (10, 2), (8, 2), (8, 4), (7, 2), (7, 4), (6, 4), (5, 4), (4, 4), (3, 4), (2, 4)]

@@ -179,6 +179,8 @@ static inline WgradArgs wgrad_args(const e2_tensor5& x, const e2_tensor5& dy, fl
 //   WK == 8                          ... one tile per work-group, waves split positions pw_wgrad_ks
 //   WK == 9                          ... for kernels with taps                          wgrad_ks
 //       (8 / 9 with BP >= 1: the "even" form, PS work-groups over BP bands)
+//   WK == 18 / 19                    8 / 9 with every f32 product made of six bf16
+//                                    MFMA products (same families, same BP / PS)       pw_wgrad_ks / wgrad_ks
 //   dy padded, WK in {1, 14, 101, 114}, BP in {128, 256}
 //                                    the direct kernel; WK % 100 == 14: the waves split
 //                                    the quads; WK >= 100: XCD-grouped block order      wgrad_direct
@@ -198,6 +200,7 @@ struct E2WgradRoute {
   bool xcd = false;             // DIRECT: WK >= 100
   int splits = 0;               // PS: position splits (even form: the number of work-groups)
   int bands = 0, groups = 0;    // PW_KS / KS, even form: BP bands, PS work-groups (else 0)
+  bool six = false;             // PW_KS / KS: WK 18 / 19, six bf16 products per f32 product
   const char* refuse = nullptr; // non-null: no kernel runs these integers, and why
 };
 static inline E2WgradRoute e2_wgrad_route(const int v[5], bool dy_padded) {
@@ -205,8 +208,9 @@ static inline E2WgradRoute e2_wgrad_route(const int v[5], bool dy_padded) {
   const int WK = v[2], BP = v[3];
   r.MT = v[0]; r.NT = v[1]; r.splits = v[4];
   if (WK == 7) { r.family = E2_WG_PW; return r; }
-  if (WK == 8 || WK == 9) {
-    r.family = WK == 8 ? E2_WG_PW_KS : E2_WG_KS;
+  if (WK == 8 || WK == 9 || WK == 18 || WK == 19) {
+    r.family = WK % 10 == 8 ? E2_WG_PW_KS : E2_WG_KS;
+    r.six = WK >= 18;
     if (BP >= 1) { r.bands = BP; r.groups = v[4]; }
     return r;
   }
@@ -231,11 +235,11 @@ static inline const char* e2_wgrad_family_name(const E2WgradRoute& r, bool bf16)
   return "wgrad_lds";
 }
 
-// ---- what the K-contiguous GEMMs (WK 7 / 8 / 9) can run ---------------------------------------
+// ---- what the K-contiguous GEMMs (WK 7 / 8 / 9 / 18 / 19) can run ---------------------------------------
 // The clause that refuses, or nullptr.  choose_wcfg asks (a forced 7 / 8 / 9 that gets a clause
 // takes the cost model's choice: "fallback"), and the launchers ask again through E2_REQUIRE.  The
 // clauses only the launchers have -- a forced string that meets one is an error -- stand there.
-// WK 7 and 8: a 1x1x1 kernel on dense channel planes, f32 mode
+// WK 7, 8 and 18: a 1x1x1 kernel on dense channel planes, f32 mode
 static inline const char* e2_pw_wgrad_limit(const WgradArgs& a, bool bf16, int /*input_slack*/) {
   if (!(a.kd == 1 && a.kh == 1 && a.kw == 1)) return "pointwise wgrad: the kernel is not 1x1x1";
   if (!(a.xsY == a.Wo && a.xsZ == (int64_t)a.Ho * a.Wo && a.dsY == a.Wo && a.dsZ == (int64_t)a.Ho * a.Wo))
@@ -243,7 +247,7 @@ static inline const char* e2_pw_wgrad_limit(const WgradArgs& a, bool bf16, int /
   if (bf16) return "pointwise wgrad: an f32 kernel, not offered in bf16 mode";
   return nullptr;
 }
-// WK 9: taps; the padded gradient at the input's row pitch with >= 31 zeros behind a plane; f32
+// WK 9 and 19: taps; the padded gradient at the input's row pitch with >= 31 zeros behind a plane; f32
 // mode; 128 readable bytes behind x; 32-bit byte offsets inside a sample
 static inline const char* e2_wgrad_ks_limit(const WgradArgs& a, bool bf16, int input_slack) {
   const int64_t Din = a.Do + a.kd - 1, Hin = a.Ho + a.kh - 1;

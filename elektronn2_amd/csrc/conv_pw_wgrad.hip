@@ -69,6 +69,53 @@ __device__ __forceinline__ f32x4 pg_load(const float* row, int k, int K) {
   return v;
 }
 
+// ---- f32 products from six bf16 MFMAs ("MT,NT,18,..." / "MT,NT,19,...", DESIGN.md finding 60) ----
+// An f32 value is EXACTLY hi + mid + lo, three bf16 pieces of 8 + 8 + 8 mantissa bits: hi = the top
+// 16 bits of x (truncated, so hi never rounds up to inf), r1 = x - hi (exact), mid = the top 16
+// bits of r1, r2 = r1 - mid (exact), lo = the top 16 bits of r2 (all that is left).  Of the nine
+// piece products of a * b the six with a combined rank <= 4 carry everything above 2^-23 |a b|;
+// mid*lo, lo*mid and lo*lo are dropped.  Every piece product is exact in f32 and the MFMA sums in
+// f32, smallest products first.  A lane's 8 values of a unit (two float4: positions 4q .. 4q+3
+// and 16 + 4q .. 16 + 4q+3 of its row) are the 8 k-values of its row in ONE
+// v_mfma_f32_16x16x32_bf16; A and B permute the 32 positions alike, so no lane shuffles.
+// Special values: NaN stays NaN (hi or mid is a NaN); +-inf gives NaN (r1 = inf - inf) where the
+// f32 form could give inf; a huge FINITE value (the 1e30 the tests put behind x) has finite
+// pieces and still contributes exactly 0 against dy's zero border.  Pieces below 2^-126 may be
+// flushed by the matrix pipe: their products are below the smallest normal f32 anyway.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+struct Pc3 { u32x4 p[3]; };                          // hi, mid, lo: 8 bf16 each
+
+// 4 AND + 2 packed subtractions + 3 packs per PAIR of values = 4.5 VALU operations per value
+__device__ __forceinline__ Pc3 pg_split8(const f32x4 (&d)[2]) {
+  Pc3 f;
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      f32x2 r = {d[h][2 * e], d[h][2 * e + 1]};
+#pragma unroll
+      for (int pc = 0; pc < 3; ++pc) {
+        const unsigned t0 = __float_as_uint(r[0]) & 0xffff0000u, t1 = __float_as_uint(r[1]) & 0xffff0000u;
+        f.p[pc][2 * h + e] = (t0 >> 16) | t1;        // (element 2e in the low half)
+        if (pc < 2) r -= f32x2{__uint_as_float(t0), __uint_as_float(t1)};
+      }
+    }
+  return f;
+}
+// the six products of one row block, TERM-major: consecutive MFMAs go to different accumulators
+template <int NT>
+__device__ __forceinline__ void pg_mfma6(const Pc3& a, const Pc3 (&b)[NT], f32x4 (&acc)[NT]) {
+  constexpr int TA[6] = {1, 0, 2, 0, 1, 0}, TB[6] = {1, 2, 0, 1, 0, 0};   // mid*mid, hi*lo, lo*hi, hi*mid, mid*hi, hi*hi
+#pragma unroll
+  for (int t = 0; t < 6; ++t)
+#pragma unroll
+    for (int nb = 0; nb < NT; ++nb)
+      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a.p[TA[t]]),
+                                                        __builtin_bit_cast(bf16x8, b[nb].p[TB[t]]), acc[nb], 0, 0, 0);
+}
+
 template <int MT, int NT>
 __global__ __launch_bounds__(256) void pw_wgrad_kernel(PgP p) {
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, q = lane >> 4;
@@ -171,7 +218,84 @@ __global__ __launch_bounds__(256) void pw_wgrad_kernel(PgP p) {
 // float4 of the NEXT unit are requested right after block mb's MFMAs of this unit, so every
 // load has a whole unit (13 x 2 x 8 MFMAs = 2.8 us) to arrive -- B double-buffered.  Units are
 // WHOLE; the K % 32 last positions of the samples are a masked step of the last range's work-groups.
+// The unit loop of both kernels below in the six-product form: this wave's units u0, u0 + 4, ...
+// (cnt > 0 of them) into acc.  B is split ONCE per unit and its pieces serve all MT blocks; A is
+// split per block, block mb + 1's split next to block mb's MFMAs (one wave per SIMD: the shadow of
+// its own MFMAs is all there is to hide the VALU work in); the last block splits the NEXT unit's
+// B and A[0].  A register set is free as soon as it is split, so every load is requested a whole
+// unit ahead: A single-buffered, B as raw values of the next unit + pieces of this one.
 template <int MT, int NT, bool TAPS>
+__device__ __forceinline__ void pg_six_units(const PgP& p, int u0, int cnt, const unsigned (&aoff)[MT],
+                                             const unsigned (&boff)[NT], f32x4 (&acc)[MT][NT]) {
+  auto where = [&](int i, const char*& ap, const char*& bp, unsigned& kb, unsigned& zb) {
+    const int u = u0 + 4 * i;
+    const int pl = u / p.stepsPerSample;
+    kb = (unsigned)(u - pl * p.stepsPerSample) * 128u;
+    if (TAPS) {
+      const int n = pl / p.planes, z = pl - n * p.planes;
+      ap = reinterpret_cast<const char*>(p.a + (long)n * p.asN + (long)z * p.asZ);
+      bp = reinterpret_cast<const char*>(p.b + (long)n * p.bsN);
+      zb = (unsigned)(z * p.bsZ) * 4u;
+    } else {
+      ap = reinterpret_cast<const char*>(p.a + (long)pl * p.asN);
+      bp = reinterpret_cast<const char*>(p.b + (long)pl * p.bsN);
+      zb = 0;
+    }
+  };
+  auto bo = [&](int nb, unsigned kb, unsigned zb) -> unsigned {
+    return TAPS ? boff[nb] + zb + kb : boff[nb] + kb;
+  };
+  auto load2 = [&](f32x4 (&d)[2], const char* base, unsigned off) {
+    const char* r = base + off;                      // (4-byte aligned only)
+    __builtin_memcpy(&d[0], r, 16);
+    __builtin_memcpy(&d[1], r + 64, 16);
+  };
+  f32x4 A[MT][2], Bn[NT][2];
+  Pc3 Ap, Bp[NT];
+  const char *ap, *bp;
+  unsigned kb, zb;
+  where(0, ap, bp, kb, zb);
+#pragma unroll
+  for (int nb = 0; nb < NT; ++nb) load2(Bn[nb], bp, bo(nb, kb, zb));
+#pragma unroll
+  for (int mb = 0; mb < MT; ++mb) load2(A[mb], ap, aoff[mb] + kb);
+#pragma unroll
+  for (int nb = 0; nb < NT; ++nb) Bp[nb] = pg_split8(Bn[nb]);
+  Ap = pg_split8(A[0]);
+  // (the last trips request their own unit again: L1 / L2 hits, nothing waits for them)
+  where(min(1, cnt - 1), ap, bp, kb, zb);
+#pragma unroll
+  for (int nb = 0; nb < NT; ++nb) load2(Bn[nb], bp, bo(nb, kb, zb));
+  load2(A[0], ap, aoff[0] + kb);
+  // ONE loop body (accumulators stay where they are); (ap, kb) = where unit i + 1 is
+#pragma unroll 1
+  for (int i = 0; i < cnt; ++i) {
+    Pc3 Bq[NT];
+#pragma unroll
+    for (int mb = 0; mb < MT; ++mb) {
+      Pc3 An;
+      if (mb + 1 < MT) {
+        An = pg_split8(A[mb + 1]);
+        load2(A[mb + 1], ap, aoff[mb + 1] + kb);
+      } else {
+        An = pg_split8(A[0]);
+#pragma unroll
+        for (int nb = 0; nb < NT; ++nb) Bq[nb] = pg_split8(Bn[nb]);
+        where(min(i + 2, cnt - 1), ap, bp, kb, zb);
+#pragma unroll
+        for (int nb = 0; nb < NT; ++nb) load2(Bn[nb], bp, bo(nb, kb, zb));
+        load2(A[0], ap, aoff[0] + kb);
+      }
+      pg_mfma6<NT>(Ap, Bp, acc[mb]);
+      Ap = An;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int nb = 0; nb < NT; ++nb) Bp[nb] = Bq[nb];
+  }
+}
+
+template <int MT, int NT, bool TAPS, bool SIX = false>
 __global__ __launch_bounds__(256) void pw_wgrad_ks_kernel(PgP p) {
   extern __shared__ float red[];
   constexpr int RW = 16 * NT + 4;                    // padded row of a wave's partial tile
@@ -252,7 +376,9 @@ __global__ __launch_bounds__(256) void pw_wgrad_ks_kernel(PgP p) {
     __builtin_memcpy(&d[1], r + 64, 16);
   };
 
-  if (cnt > 0) {
+  if constexpr (SIX) {
+    if (cnt > 0) pg_six_units<MT, NT, TAPS>(p, u0, cnt, aoff, boff, acc);
+  } else if (cnt > 0) {
     f32x4 A[MT][2], Bc[NT][2], Bn[NT][2];
     const char *ap, *bp;
     unsigned kb, zb;
@@ -358,7 +484,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_ks_kernel(PgP p) {
 // runs one segment per tile -- zero, multiply, sum through LDS, flush with atomics -- so a tile
 // has any number of producers.  A kernel of its own: pw_wgrad_ks_kernel keeps its instruction
 // stream.  The segment loop has ONE exit and is never unrolled (DESIGN.md lessons 5 and 10).
-template <int MT, int NT, bool TAPS>
+template <int MT, int NT, bool TAPS, bool SIX = false>
 __global__ __launch_bounds__(256) void pw_wgrad_ev_kernel(PgP p, WgEven ev) {
   extern __shared__ float red[];
   constexpr int RW = 16 * NT + 4;                    // padded row of a wave's partial tile
@@ -433,7 +559,9 @@ __global__ __launch_bounds__(256) void pw_wgrad_ev_kernel(PgP p, WgEven ev) {
       __builtin_memcpy(&d[1], r + 64, 16);
     };
 
-    if (cnt > 0) {
+    if constexpr (SIX) {
+      if (cnt > 0) pg_six_units<MT, NT, TAPS>(p, u0, cnt, aoff, boff, acc);
+    } else if (cnt > 0) {
       f32x4 A[MT][2], Bc[NT][2], Bn[NT][2];
       const char *ap, *bp;
       unsigned kb, zb;
@@ -535,11 +663,11 @@ __global__ __launch_bounds__(256) void pw_wgrad_ev_kernel(PgP p, WgEven ev) {
 #endif
 }
 
-template <int MT, int NT, bool TAPS>
+template <int MT, int NT, bool TAPS, bool SIX>
 int launch_ev(e2_ctx* ctx, const PgP& p, const WgEven& ev) {
   const int lds = 4 * 16 * MT * (16 * NT + 4) * (int)sizeof(float);
   static bool raised = false;
-  if (int rc = e2i_raise_lds(reinterpret_cast<const void*>(&pw_wgrad_ev_kernel<MT, NT, TAPS>), lds, &raised)) return rc;
+  if (int rc = e2i_raise_lds(reinterpret_cast<const void*>(&pw_wgrad_ev_kernel<MT, NT, TAPS, SIX>), lds, &raised)) return rc;
   PgP ps = p;
 #ifdef E2_DEBUG_ENV
   // debug build: do the work-groups that flush twice (or more) set the kernel's duration?
@@ -550,7 +678,7 @@ int launch_ev(e2_ctx* ctx, const PgP& p, const WgEven& ev) {
     E2_CHECK_HIP(hipMemsetAsync(ps.stamps, 0, sizeof(unsigned long long) * 8 * grid, ctx->stream));
   }
 #endif
-  hipLaunchKernelGGL((pw_wgrad_ev_kernel<MT, NT, TAPS>), dim3((unsigned)ev.G), dim3(256), lds, ctx->stream, ps, ev);
+  hipLaunchKernelGGL((pw_wgrad_ev_kernel<MT, NT, TAPS, SIX>), dim3((unsigned)ev.G), dim3(256), lds, ctx->stream, ps, ev);
   E2_CHECK_HIP(hipGetLastError());
 #ifdef E2_DEBUG_ENV
   if (stamps) {
@@ -591,11 +719,11 @@ static int even_split(const PgP& p, long G, int B, WgEven* ev) {
   return 0;
 }
 
-template <int MT, int NT, bool TAPS>
+template <int MT, int NT, bool TAPS, bool SIX>
 int launch_ks(e2_ctx* ctx, const PgP& p, long grid) {
   const int lds = 4 * 16 * MT * (16 * NT + 4) * (int)sizeof(float);
   static bool raised = false;
-  if (int rc = e2i_raise_lds(reinterpret_cast<const void*>(&pw_wgrad_ks_kernel<MT, NT, TAPS>), lds, &raised)) return rc;
+  if (int rc = e2i_raise_lds(reinterpret_cast<const void*>(&pw_wgrad_ks_kernel<MT, NT, TAPS, SIX>), lds, &raised)) return rc;
 #ifdef E2_DEBUG_ENV
   // in-kernel timeline (debug build): mean s_memtime ticks between the stamps over the work-groups
   PgP ps = p;
@@ -604,7 +732,7 @@ int launch_ks(e2_ctx* ctx, const PgP& p, long grid) {
     E2_CHECK_HIP(hipMalloc(&ps.stamps, sizeof(unsigned long long) * 8 * grid));
     E2_CHECK_HIP(hipMemsetAsync(ps.stamps, 0, sizeof(unsigned long long) * 8 * grid, ctx->stream));
   }
-  hipLaunchKernelGGL((pw_wgrad_ks_kernel<MT, NT, TAPS>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, ps);
+  hipLaunchKernelGGL((pw_wgrad_ks_kernel<MT, NT, TAPS, SIX>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, ps);
   E2_CHECK_HIP(hipGetLastError());
   if (stamps) {
     E2_CHECK_HIP(hipStreamSynchronize(ctx->stream));
@@ -626,7 +754,7 @@ int launch_ks(e2_ctx* ctx, const PgP& p, long grid) {
     (void)hipFree(ps.stamps);
   }
 #else
-  hipLaunchKernelGGL((pw_wgrad_ks_kernel<MT, NT, TAPS>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, p);
+  hipLaunchKernelGGL((pw_wgrad_ks_kernel<MT, NT, TAPS, SIX>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, p);
   E2_CHECK_HIP(hipGetLastError());
 #endif
   return 0;
@@ -677,8 +805,9 @@ int ks_split(e2_ctx* ctx, const WgradArgs& a, const E2WgradRoute& r, long units,
   return 0;
 }
 template <int MT, int NT, bool TAPS>
-int launch_split(e2_ctx* ctx, const PgP& p, const KsSplit& k) {
-  return k.even ? launch_ev<MT, NT, TAPS>(ctx, p, k.ev) : launch_ks<MT, NT, TAPS>(ctx, p, k.grid);
+int launch_split(e2_ctx* ctx, const PgP& p, const KsSplit& k, bool six) {
+  if (six) return k.even ? launch_ev<MT, NT, TAPS, true>(ctx, p, k.ev) : launch_ks<MT, NT, TAPS, true>(ctx, p, k.grid);
+  return k.even ? launch_ev<MT, NT, TAPS, false>(ctx, p, k.ev) : launch_ks<MT, NT, TAPS, false>(ctx, p, k.grid);
 }
 
 }  // namespace
@@ -714,6 +843,7 @@ int e2i_pw_wgrad(e2_ctx* ctx, const WgradArgs& a, const E2WgradRoute& r) {
 
 // "MT,NT,8,0,S": the waves of a work-group split the positions (pw_wgrad_ks_kernel);
 // "MT,NT,8,B,G", B >= 1: G work-groups with even position ranges in B bands (pw_wgrad_ev_kernel)
+// ("MT,NT,18,...": the same launches with six bf16 products per f32 product, r.six)
 int e2i_pw_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, const E2WgradRoute& r) {
   const char* limit = e2_pw_wgrad_limit(a, ctx->mfma_bf16 != 0, ctx->input_slack);
   E2_REQUIRE(!limit, "%s", limit);
@@ -731,14 +861,15 @@ int e2i_pw_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, const E2WgradRoute& r) {
   p.rem = (int)(K % 32);
   KsSplit k;
   if (int rc = ks_split(ctx, a, r, (long)a.N * p.stepsPerSample, "pointwise wgrad", p, &k)) return rc;
-#define E2_L(M, N_) if (r.MT == M && r.NT == N_) return launch_split<M, N_, false>(ctx, p, k);
+#define E2_L(M, N_) if (r.MT == M && r.NT == N_) return launch_split<M, N_, false>(ctx, p, k, r.six);
   E2_L(13, 2) E2_L(7, 2) E2_L(7, 4) E2_L(4, 4) E2_L(10, 2)
 #undef E2_L
   e2_set_error("pointwise wgrad (position-split waves): no instance MT=%d NT=%d", r.MT, r.NT);
   return 2;
 }
 
-// "MT,NT,9,0,S" (and "MT,NT,9,B,G", B >= 1: even position ranges, pw_wgrad_ev_kernel): the SAME
+// "MT,NT,9,0,S" (and "MT,NT,9,B,G", B >= 1: even position ranges, pw_wgrad_ev_kernel; "MT,NT,19,...":
+// either with six bf16 products per f32 product): the SAME
 // kernel for a conv with taps (T = kd * kh * kw > 1).  dy lives in the interior of its zero-padded buffer at the INPUT's row pitch (WgradArgs.dy_padded), so over the
 // memory span of a plane -- K = (Ho - 1) * pitch + Wo positions, zeros in the kw - 1 gap columns
 // -- tap (tz, ty, tx) of input channel ci is the channel's plane read at the constant shift
@@ -777,7 +908,7 @@ int e2i_wgrad_ks(e2_ctx* ctx, const WgradArgs& a, const E2WgradRoute& r) {
   p.stepsPerSample = (int)((K + 31) / 32);                    // (whole units of a PLANE)
   KsSplit k;
   if (int rc = ks_split(ctx, a, r, (long)a.N * a.Do * p.stepsPerSample, "wgrad (position-split GEMM)", p, &k)) return rc;
-#define E2_L(M, N_) if (r.MT == M && r.NT == N_) return launch_split<M, N_, true>(ctx, p, k);
+#define E2_L(M, N_) if (r.MT == M && r.NT == N_) return launch_split<M, N_, true>(ctx, p, k, r.six);
   E2_L(13, 2) E2_L(7, 2) E2_L(7, 4) E2_L(4, 4) E2_L(10, 2) E2_L(5, 4) E2_L(3, 4) E2_L(2, 4) E2_L(8, 2) E2_L(8, 4) E2_L(6, 4)
 #undef E2_L
   e2_set_error("wgrad (position-split GEMM): no instance MT=%d NT=%d", r.MT, r.NT);

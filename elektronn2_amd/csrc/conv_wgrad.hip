@@ -377,8 +377,13 @@ static WCfg choose_wcfg(const e2_ctx* ctx, const WgradArgs& a, int* ok, int* src
       // with taps; a problem outside its limits takes the cost model's choice too.  Every other
       // string is returned as it is: what no kernel runs is refused by its route or its launcher.
       // (The limits: conv_host.hpp; the launchers hold clauses these two do not)
-      const char* limit = f.WK == 9 ? e2_wgrad_ks_limit(a, ctx->mfma_bf16, ctx->input_slack)
-                          : (f.WK == 7 || f.WK == 8) ? e2_pw_wgrad_limit(a, ctx->mfma_bf16, ctx->input_slack)
+      // "MT,NT,18,..." / "MT,NT,19,...": 8 / 9 with six bf16 products per f32 product, same limits --
+      // but for bf16 mode, where they are an ERROR of their launcher (the bf16 tables have keys of
+      // their own: no shipped f32 entry meets that mode, so there is nothing to fall back from).
+      const bool six = f.WK == 18 || f.WK == 19;
+      const bool bf16 = ctx->mfma_bf16 && !six;
+      const char* limit = (f.WK == 9 || f.WK == 19) ? e2_wgrad_ks_limit(a, bf16, ctx->input_slack)
+                          : (f.WK == 7 || f.WK == 8 || f.WK == 18) ? e2_pw_wgrad_limit(a, bf16, ctx->input_slack)
                           : nullptr;
       if (limit == nullptr) { *ok = 1; *src = E2_SRC_FORCED; return f; }
     }

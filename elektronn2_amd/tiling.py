@@ -29,7 +29,7 @@ from collections import namedtuple
 _LIST = re.compile(r"-?[0-9]+(,-?[0-9]+){0,7}")
 
 
-WgradRoute = namedtuple('WgradRoute', 'family MT NT WK BP wave_split xcd splits bands groups refuse')
+WgradRoute = namedtuple('WgradRoute', 'family MT NT WK BP wave_split xcd splits bands groups refuse six')
 
 
 class Tiling(namedtuple('Tiling', 'kind family v')):
@@ -55,6 +55,8 @@ def wgrad_route(t, dy_padded, bf16=False):
       WK == 8                          ... one tile per work-group, waves split positions pw_wgrad_ks
       WK == 9                          ... for kernels with taps                          wgrad_ks
           (8 / 9 with BP >= 1: the "even" form, PS work-groups over BP bands)
+      WK == 18 / 19                    8 / 9 with every f32 product made of six bf16
+                                       MFMA products (same families, same BP / PS)       pw_wgrad_ks / wgrad_ks
       dy padded, WK in {1, 14, 101, 114}, BP in {128, 256}
                                        the direct kernel; WK % 100 == 14: the waves split
                                        the quads; WK >= 100: XCD-grouped block order      wgrad_direct
@@ -66,15 +68,16 @@ def wgrad_route(t, dy_padded, bf16=False):
     A refused route keeps the family of the LDS-staged kernel (``refuse``: why).  ``dy_padded``: the
     launch comes through the padded-gradient entry point (the launch plan's always do); ``bf16``:
     the operands are rounded to bf16, which only the direct kernel's name shows.  BP is 0 where it
-    is no tile length, bands / groups are 0 outside the even form; WK is the field as written."""
+    is no tile length, bands / groups are 0 outside the even form; WK is the field as written; ``six``:
+    the six-product form (WK 18 / 19)."""
     assert t.kind == 'wgrad' and t.family == 'wgrad', t
     MT, NT, WK, BP, PS = t.v
     r = dict(family='wgrad_lds', MT=MT, NT=NT, WK=WK, BP=0, wave_split=False, xcd=False, splits=PS,
-             bands=0, groups=0, refuse=None)
+             bands=0, groups=0, refuse=None, six=False)
     if WK == 7:
         r.update(family='pw_wgrad')
-    elif WK in (8, 9):
-        r.update(family='pw_wgrad_ks' if WK == 8 else 'wgrad_ks')
+    elif WK in (8, 9, 18, 19):
+        r.update(family='pw_wgrad_ks' if WK % 10 == 8 else 'wgrad_ks', six=WK >= 18)
         if BP >= 1:
             r.update(bands=BP, groups=PS)
     elif dy_padded and WK in (1, 14, 101, 114) and BP in (128, 256):

@@ -102,7 +102,10 @@ int  e2_get_mfma_dtype(const e2_ctx* ctx);
  * every (input channel, tap) column of dW is a K-contiguous row of x at the tap's constant shift;
  * e2_conv3d_wgrad_pad only: needs the gradient at the input's row pitch, (kh - 1) input rows
  * + kw - 1 >= 31 zeros behind a gradient plane, f32 mode and e2_set_input_slack(ctx, >= 128);
- * BP positions per tile, PS position splits).  The forms 7, 8 and 9 are exempt from the rule
+ * 18 / 19 = the forms 8 / 9 with every f32 product made of six bf16 MFMA products
+ * (v_mfma_f32_16x16x32_bf16 on exact hi + mid + lo pieces of both operands: f32-accurate sums,
+ * +-inf in an operand gives NaN; an error in bf16 mode);
+ * BP positions per tile, PS position splits).  The forms 7, 8 and 9 (18, 19) are exempt from the rule
  * below: where their layout requirements are not met the call takes the cost model's choice --
  * a FALLBACK, which e2_last_launch() reports as such and e2_tiling_fallbacks() counts (the tuning
  * keys hold the row pitch, not the plane pitch, so a shipped entry can meet a view it cannot
