@@ -1300,13 +1300,18 @@ class Context:
         _chk(_lib.e2_set_loss_grad_mode(self.h, int(bool(sum_mode)), _fp(count_out)),
              "e2_set_loss_grad_mode")
 
+    def _opt_step(self, entry_name, p, g, states, seg_off, seg_reg, hyper, gdiv, gmul, zero_g):
+        """one optimiser update over the arena p: ``states`` are the rule's state arenas in the
+        order of the entry point's arguments"""
+        _chk(getattr(_lib, entry_name)(self.h, _fp(p), _fp(g), *[_fp(s) for s in states], p.numel(),
+                                       C.c_void_p(seg_off.data_ptr()), _fp(seg_reg),
+                                       seg_reg.numel(), _fp(hyper), _fp(gdiv), float(gmul),
+                                       int(bool(zero_g))), entry_name)
+
     def adam_step(self, p, g, m, s, seg_off, seg_reg, hyper, gdiv=None, gmul=1.0, zero_g=False):
         """gdiv / gmul: the update sees g * gmul / (gdiv[0] + 1e-5) (gdiv: device scalar, or
         None); zero_g: g is left zero for the next backward pass"""
-        _chk(_lib.e2_adam_step_ex(self.h, _fp(p), _fp(g), _fp(m), _fp(s), p.numel(),
-                                  C.c_void_p(seg_off.data_ptr()), _fp(seg_reg),
-                                  seg_reg.numel(), _fp(hyper), _fp(gdiv), float(gmul),
-                                  int(bool(zero_g))), "e2_adam_step_ex")
+        self._opt_step("e2_adam_step_ex", p, g, (m, s), seg_off, seg_reg, hyper, gdiv, gmul, zero_g)
 
     def make_upd_jobs(self, jobs, rests):
         """records of adam_pack_step.  jobs: (arena offset, forward image | None, data-gradient
@@ -1344,26 +1349,17 @@ class Context:
              "e2_adam_pack_step")
 
     def sgd_step(self, p, g, d, seg_off, seg_reg, hyper, gdiv=None, gmul=1.0, zero_g=False):
-        _chk(_lib.e2_sgd_step_ex(self.h, _fp(p), _fp(g), _fp(d), p.numel(),
-                                 C.c_void_p(seg_off.data_ptr()), _fp(seg_reg),
-                                 seg_reg.numel(), _fp(hyper), _fp(gdiv), float(gmul),
-                                 int(bool(zero_g))), "e2_sgd_step_ex")
+        self._opt_step("e2_sgd_step_ex", p, g, (d,), seg_off, seg_reg, hyper, gdiv, gmul, zero_g)
 
     def adagrad_step(self, p, g, h, seg_off, seg_reg, hyper, gdiv=None, gmul=1.0, zero_g=False):
         """h' = h + c g^2 (c = 2 at t = 0, else 1), p' = p - lr / sqrt(h') (g + wd r p); an element
         whose h' is 0 is left unchanged; t in hyper[4] advances (e2hip.h: e2_adagrad_step_ex)"""
-        _chk(_lib.e2_adagrad_step_ex(self.h, _fp(p), _fp(g), _fp(h), p.numel(),
-                                     C.c_void_p(seg_off.data_ptr()), _fp(seg_reg),
-                                     seg_reg.numel(), _fp(hyper), _fp(gdiv), float(gmul),
-                                     int(bool(zero_g))), "e2_adagrad_step_ex")
+        self._opt_step("e2_adagrad_step_ex", p, g, (h,), seg_off, seg_reg, hyper, gdiv, gmul, zero_g)
 
     def adadelta_step(self, p, g, s, d, seg_off, seg_reg, hyper, gdiv=None, gmul=1.0, zero_g=False):
         """s' = mom s + (1 - mom) g^2, dir = g sqrt(d + eps) / sqrt(s + eps) on the old s and d,
         d' = mom d + (1 - mom) dir^2, p' = p - lr (dir + wd mult p) (e2hip.h: e2_adadelta_step_ex)"""
-        _chk(_lib.e2_adadelta_step_ex(self.h, _fp(p), _fp(g), _fp(s), _fp(d), p.numel(),
-                                      C.c_void_p(seg_off.data_ptr()), _fp(seg_reg),
-                                      seg_reg.numel(), _fp(hyper), _fp(gdiv), float(gmul),
-                                      int(bool(zero_g))), "e2_adadelta_step_ex")
+        self._opt_step("e2_adadelta_step_ex", p, g, (s, d), seg_off, seg_reg, hyper, gdiv, gmul, zero_g)
 
     # ---- first launch of a step that may stand k times in one graph (e2hip.h: e2_step_prologue) ----
     def step_prologue(self, state, ring=None, dst=None, src=None, hist=None):

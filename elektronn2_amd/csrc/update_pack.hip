@@ -7,7 +7,7 @@
 // written: 8-12 B per parameter with the fetched padding) -- 10.5 + 14.5 us of neuro3d_lite's
 // 1.52 ms, 19.3 + 31.9 us of neuro3d's 1.74 ms.  Here a work-group owns a TILE of one conv's
 // weight tensor -- 32 output channels x IC input channels x the taps of one kernel plane --,
-// applies the update to it (the same arithmetic, in the same order, as adam_kernel: results are
+// applies the update to it (AdamRule of opt_rules.hpp, the rule adam_kernel runs: results are
 // bit-identical), keeps the new values in LDS and writes them a second and third time as the
 // tile of the forward image Wp[dz][ci / 4][t][ci % 4][co] (taps flipped) and of the
 // data-gradient image Wp[dz][co / 4][t][co % 4][ci]: both along their contiguous axis, 128 B per
@@ -26,9 +26,8 @@
 // image writes alone take what pack_multi_kernel takes (36 us with zeros as source).  Kept as an
 // entry point, plan option adam_pack OFF.
 #include "stream_common.hpp"
+#include "opt_rules.hpp"
 #include <algorithm>
-
-#define E2_EPS_ADAM 1e-5f
 
 namespace {
 
@@ -53,17 +52,6 @@ struct UpdJob {
 
 struct UpdRest { long off, n; float reg; int pad; };
 
-__device__ __forceinline__ float adam1(float& p, float g, float& m, float& s, float mom, float b2,
-                                       float fac, float mult, float lr) {
-  const float nm = mom * m + (1.f - mom) * g;
-  const float ns = b2 * s + (1.f - b2) * g * g;
-  float dir = fac * nm / sqrtf(ns + E2_EPS_ADAM);
-  if (mult != 0.f) dir += mult * p;
-  p = p - lr * dir;
-  m = nm; s = ns;
-  return p;
-}
-
 constexpr int kMaxJobs = 96;
 constexpr int kUT = 1024;     // threads per work-group: a tile's update is a chain of load -> compute -> store
                               // trips per thread, and what hides their latency is threads (two work-groups per CU)
@@ -77,9 +65,7 @@ __global__ __launch_bounds__(kUT) void adam_pack_kernel(float* __restrict__ p, f
   extern __shared__ __attribute__((aligned(16))) float tile[];
   __shared__ int jt0[kMaxJobs + 1];
   for (int i = threadIdx.x; i <= njobs; i += kUT) jt0[i] = i < njobs ? jobs[i].tile0 : ntiles;
-  const float lr = hyper[0], mom = hyper[1], b2 = hyper[2], wd = hyper[3];
-  const float t = hyper[4] + 1.f;
-  const float fac = sqrtf(1.f - powf(b2, t)) / (1.f - powf(mom, t));
+  const AdamRule rule(hyper);
   const float gs = gdiv ? gmul / (gdiv[0] + 1e-5f) : gmul;
   const int tid = threadIdx.x;
   __syncthreads();
@@ -98,7 +84,7 @@ __global__ __launch_bounds__(kUT) void adam_pack_kernel(float* __restrict__ p, f
     const bool anyF = j.wpF && oc0 < j.coWF && ic0 < j.icWF;
     const bool anyD = j.wpD && ic0 < j.coWD && oc0 < j.icWD;
     if (!anyF && !anyD) continue;
-    const float mult = j.reg * wd;
+    const float mult = rule.mult(j.reg);
     const bool real = oc0 < j.cout && ic0 < j.cin;     // (else: padding only -- zeros, no LDS trip)
     // ---- the update, tensor order: consecutive threads walk (ci, tap) of one output channel.
     // U elements per thread and trip, every load issued before the first store: g is read AND
@@ -107,7 +93,7 @@ __global__ __launch_bounds__(kUT) void adam_pack_kernel(float* __restrict__ p, f
       constexpr int U = 4;
       for (int e0 = tid; e0 < 32 * KT; e0 += kUT * U) {
         long ix[U]; int la[U]; bool ok[U];
-        float gv[U], pv[U], mv[U], sv[U];
+        float gv[U], pv[U], ms[U][2];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int e = e0 + kUT * u;
@@ -121,15 +107,16 @@ __global__ __launch_bounds__(kUT) void adam_pack_kernel(float* __restrict__ p, f
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          if (ok[u]) { gv[u] = g[ix[u]]; pv[u] = p[ix[u]]; mv[u] = m[ix[u]]; sv[u] = s[ix[u]]; }
+          if (ok[u]) { gv[u] = g[ix[u]]; pv[u] = p[ix[u]]; ms[u][0] = m[ix[u]]; ms[u][1] = s[ix[u]]; }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           float v = 0.f;
           if (ok[u]) {
             float gq = gv[u];
             if (gs != 1.f) gq *= gs;
-            v = adam1(pv[u], gq, mv[u], sv[u], mom, b2, fac, mult, lr);
-            p[ix[u]] = pv[u]; m[ix[u]] = mv[u]; s[ix[u]] = sv[u];
+            rule.apply(pv[u], gq, ms[u], mult);
+            v = pv[u];
+            p[ix[u]] = pv[u]; m[ix[u]] = ms[u][0]; s[ix[u]] = ms[u][1];
             if (zero_g) g[ix[u]] = 0.f;
           }
           if (la[u] >= 0) tile[la[u]] = v;
@@ -167,15 +154,15 @@ __global__ __launch_bounds__(kUT) void adam_pack_kernel(float* __restrict__ p, f
   // ---- everything without images: the plain update ------------------------------------------
   for (int r = 0; r < nrest; ++r) {
     const UpdRest q = rest[r];
-    const float mult = q.reg * wd;
+    const float mult = rule.mult(q.reg);
     for (long i = blockIdx.x * (long)kUT + tid; i < q.n; i += (long)gridDim.x * kUT) {
       const long a = q.off + i;
       float gv = g[a];
       if (gs != 1.f) gv *= gs;
       if (zero_g) g[a] = 0.f;
-      float pv = p[a], mv = m[a], sv = s[a];
-      adam1(pv, gv, mv, sv, mom, b2, fac, mult, lr);
-      p[a] = pv; m[a] = mv; s[a] = sv;
+      float pv = p[a], ms[2] = {m[a], s[a]};
+      rule.apply(pv, gv, ms, mult);
+      p[a] = pv; m[a] = ms[0]; s[a] = ms[1];
     }
   }
   // publish t once every work-group has read the old value.  Up to 4 x CUs work-groups: 16
@@ -193,8 +180,7 @@ __global__ __launch_bounds__(kUT) void adam_pack_kernel(float* __restrict__ p, f
       const unsigned pt = __hip_atomic_fetch_add(top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (pt == ntop - 1) {
         __hip_atomic_store(top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        hyper[4] = t;
-        hyper[5] = fac;
+        rule.publish(hyper);
       }
     }
   }

@@ -13,6 +13,10 @@ not kept (its only call site is commented out in the reference, trainer.py:207);
 what ``repair()`` resets of an optimiser's own state is ``clear_last_dir()``.
 AdaGrad leaves an element whose squared-gradient sum is still 0 unchanged, where
 the reference divides by sqrt(0) (class AdaGrad).
+
+A class declares its state arenas in ``_state`` -- (checkpoint key, attribute) pairs in
+the order of the launch's arguments -- and its launch in ``_launch``; ``Optimiser``
+allocates, parks, saves, loads and launches over that table, ``_StepCounter`` adds ``t``.
 """
 from __future__ import annotations
 
@@ -42,8 +46,13 @@ class Optimiser(object):
         cls.global_mom.set_value(graphutils.as_floatX(val))
 
     step_name = None
+    _state = ()         # (checkpoint key, attribute) per state arena, in the order of the launch's arguments
+    _launch = None      # the backend method that runs the update
 
     def __init__(self, inputs, loss, params, additional_outputs, model):
+        for _, attr in self._state:
+            setattr(self, attr, None)
+        self._pending = None
         self.meta_params = dict(lr=self.global_lr, mom=self.global_mom,
                                 wd=self.global_weight_decay)
         self.input = inputs
@@ -161,12 +170,29 @@ class Optimiser(object):
         self.step.last_exec_time = t
         return losses, t
 
-    # subclasses
+    # ---- the state arenas of ``_state``: made by the first step, parked in ``_pending`` until then ----
+    def _arenas(self):
+        """the state arenas, or None before the first step has made them"""
+        arenas = [getattr(self, attr) for _, attr in self._state]
+        return None if arenas[0] is None else arenas
+
     def _ensure_state(self, plan):
-        raise NotImplementedError
+        if self._arenas() is None:
+            for _, attr in self._state:
+                setattr(self, attr, plan.zeros_flat(max(self.model.n_train, 4)))
+        if self._pending is not None:
+            self._apply(self._pending)
+            self._pending = None
 
     def device_update(self, plan):
-        raise NotImplementedError
+        m = self.model
+        getattr(plan.ctx, self._launch)(m.P[:m.n_train] if m.n_train < m.P.numel() else m.P, m.G,
+                                        *self._arenas(), m.seg_off, m.seg_reg, self._hyper,
+                                        **self._grad_scaling(plan))
+
+    def _zero_state(self):
+        for a in self._arenas() or ():
+            a.zero_()
 
     def _grad_scaling(self, plan):
         """keyword arguments of the update launch: the data-parallel normalisation applied
@@ -180,67 +206,66 @@ class Optimiser(object):
                 kw['gmul'] = sc[1]
         return kw
 
-    def state_dict(self):
+    def _counter_state(self):
+        """what a step counter adds to a state_dict that is not empty (_StepCounter)"""
         return {}
 
-    def load_state_dict(self, d):
+    def _load_t(self, d):
         pass
 
     def _apply_pending_hyper(self):
         pass
 
+    def state_dict(self):
+        keys = [k for k, _ in self._state]
+        arenas = self._arenas()
+        if arenas is None:
+            # loaded but not stepped yet (modelload(f) followed by save()): the state is still
+            # parked in _pending (the step counter in _pending_t) -- hand it on, so
+            # load -> save -> load does not drop it
+            if self._pending is None or keys[0] not in self._pending:
+                return {}
+            d = dict((k, np.array(self._pending[k], dtype=np.float32)) for k in keys)
+        else:
+            d = dict((k, a.cpu().numpy()) for k, a in zip(keys, arenas))
+        d.update(self._counter_state())
+        return d
+
+    def _apply(self, d):
+        import torch
+        keys = [k for k, _ in self._state]
+        if keys[0] in d:
+            arenas = self._arenas()
+            n = arenas[0].numel()
+            vals = [np.ascontiguousarray(d[k], dtype=np.float32) for k in keys]
+            if any(v.size != n for v in vals):
+                raise ValueError("%s state of %i elements does not fit this model (%i)"
+                                 % (self.step_name, vals[0].size, n))
+            for a, v in zip(arenas, vals):
+                a.copy_(torch.from_numpy(v))
+
+    def load_state_dict(self, d):
+        """the state arenas and, where there is one, the step counter t.  The device buffers are
+        created lazily by the first step; a state loaded before that (``create_model();
+        modelload(f, model)``) is kept and applied when they exist, so resuming continues the
+        moments and the bias correction (Adam) and does not double its first gradient again
+        (AdaGrad) instead of silently restarting them."""
+        if self._arenas() is None:
+            self._pending = {k: d[k] for k, _ in self._state if k in d} or None
+        else:
+            self._apply(d)
+        self._load_t(d)
+
 
 class SGD(Optimiser):
     """d' = g + mom*d ; p' = p - lr*(d' + wd*p [*apply_reg])  (optimiser.py:146-160)."""
     step_name = 'SGD'
-
-    def __init__(self, *a):
-        self.last_dir = None
-        self._pending = None
-        super(SGD, self).__init__(*a)
-
-    def _ensure_state(self, plan):
-        if self.last_dir is None:
-            self.last_dir = plan.zeros_flat(max(self.model.n_train, 4))
-        if self._pending is not None:
-            self._apply(self._pending)
-            self._pending = None
-
-    def device_update(self, plan):
-        m = self.model
-        plan.ctx.sgd_step(m.P[:m.n_train] if m.n_train < m.P.numel() else m.P, m.G,
-                          self.last_dir, m.seg_off, m.seg_reg, self._hyper,
-                          **self._grad_scaling(plan))
+    _state = (('last_dir', 'last_dir'),)
+    _launch = 'sgd_step'
 
     def clear_last_dir(self):
-        if self.last_dir is not None:
-            self.last_dir.zero_()
-
-    def state_dict(self):
-        if self.last_dir is None:
-            # a state loaded into a model that has not stepped yet is still parked in
-            # _pending: hand it on, so load -> save -> load does not drop it
-            if self._pending is not None and 'last_dir' in self._pending:
-                return {'last_dir': np.array(self._pending['last_dir'], dtype=np.float32)}
-            return {}
-        return {'last_dir': self.last_dir.cpu().numpy()}
-
-    def _apply(self, d):
-        import torch
-        if 'last_dir' in d:
-            v = np.ascontiguousarray(d['last_dir'], dtype=np.float32)
-            if v.size != self.last_dir.numel():
-                raise ValueError("SGD state of %i elements does not fit this model (%i)"
-                                 % (v.size, self.last_dir.numel()))
-            self.last_dir.copy_(torch.from_numpy(v))
-
-    def load_state_dict(self, d):
-        """the buffers are created lazily by the first step: a state loaded into a fresh
-        model is kept and applied when they exist (``create_model(); modelload(f, model)``)"""
-        if self.last_dir is None:
-            self._pending = dict(d)
-        else:
-            self._apply(d)
+        """the buffer back to zero; a state that is still parked stays"""
+        self._zero_state()
 
 
 class _StepCounter(object):
@@ -253,6 +278,9 @@ class _StepCounter(object):
         if self._hyper is None:
             return 0.0 if self._pending_t is None else float(self._pending_t)
         return float(self._hyper[4].item())
+
+    def _counter_state(self):
+        return {'t': np.array(self.t)}
 
     def _apply_pending_hyper(self):
         if self._pending_t is not None:
@@ -270,72 +298,25 @@ class Adam(_StepCounter, Optimiser):
     """optimiser.py:273-334: eps = 1e-5 INSIDE the sqrt, bias factor
     sqrt(1-beta2^t)/(1-mom^t), L2 term outside the adaptive scaling."""
     step_name = 'Adam'
+    _state = (('m', 'momentum'), ('s', 'squared_accum'))
+    _launch = 'adam_step'
 
     def __init__(self, *a):
         self.beta2 = VariableParam(value=0.999, name='beta2', dtype=graphutils.floatX)
-        self.squared_accum = None
-        self.momentum = None
-        self._pending = None
-        self._pending_t = None
         super(Adam, self).__init__(*a)
         self.meta_params['beta2'] = self.beta2
 
     def _beta2(self):
         return self.beta2.get_value()
 
-    def _ensure_state(self, plan):
-        if self.momentum is None:
-            n = max(self.model.n_train, 4)
-            self.momentum = plan.zeros_flat(n)
-            self.squared_accum = plan.zeros_flat(n)
-        if self._pending is not None:
-            self._apply(self._pending)
-            self._pending = None
-
     def device_update(self, plan):
-        m = self.model
         if getattr(plan, '_upd', None) is not None:
             # the update that also writes the packed conv weight images (csrc/update_pack.hip)
+            m = self.model
             plan.ctx.adam_pack_step(m.P, m.G, self.momentum, self.squared_accum, plan._upd,
                                     self._hyper, **self._grad_scaling(plan))
             return
-        plan.ctx.adam_step(m.P[:m.n_train] if m.n_train < m.P.numel() else m.P, m.G,
-                           self.momentum, self.squared_accum, m.seg_off, m.seg_reg,
-                           self._hyper, **self._grad_scaling(plan))
-
-    def state_dict(self):
-        if self.momentum is None:
-            # loaded but not stepped yet (modelload(f) followed by save()): the moments and
-            # the step counter are still parked in _pending / _pending_t -- hand them on
-            if self._pending is not None and 'm' in self._pending:
-                return {'m': np.array(self._pending['m'], dtype=np.float32),
-                        's': np.array(self._pending['s'], dtype=np.float32),
-                        't': np.array(self.t)}
-            return {}
-        return {'m': self.momentum.cpu().numpy(), 's': self.squared_accum.cpu().numpy(),
-                't': np.array(self.t)}
-
-    def _apply(self, d):
-        import torch
-        if 'm' in d:
-            m = np.ascontiguousarray(d['m'], dtype=np.float32)
-            s = np.ascontiguousarray(d['s'], dtype=np.float32)
-            if m.size != self.momentum.numel() or s.size != self.momentum.numel():
-                raise ValueError("Adam state of %i elements does not fit this model (%i)"
-                                 % (m.size, self.momentum.numel()))
-            self.momentum.copy_(torch.from_numpy(m))
-            self.squared_accum.copy_(torch.from_numpy(s))
-
-    def load_state_dict(self, d):
-        """m, s and the step counter t.  The device buffers are created lazily by the
-        first step; a state loaded before that (``create_model(); modelload(f, model)``)
-        is kept and applied when they exist, so resuming continues the bias correction
-        and the moments instead of silently restarting them."""
-        if self.momentum is None:
-            self._pending = {k: d[k] for k in ('m', 's') if k in d} or None
-        else:
-            self._apply(d)
-        self._load_t(d)
+        super(Adam, self).device_update(plan)
 
 
 class AdaGrad(_StepCounter, Optimiser):
@@ -353,59 +334,15 @@ class AdaGrad(_StepCounter, Optimiser):
       left unchanged and its h stays 0.
     ``t`` counts the steps on the device, as Adam's does."""
     step_name = 'AdaGrad'
-
-    def __init__(self, *a):
-        self.hs = None
-        self._pending = None
-        self._pending_t = None
-        super(AdaGrad, self).__init__(*a)
-
-    def _ensure_state(self, plan):
-        if self.hs is None:
-            self.hs = plan.zeros_flat(max(self.model.n_train, 4))
-        if self._pending is not None:
-            self._apply(self._pending)
-            self._pending = None
-
-    def device_update(self, plan):
-        m = self.model
-        plan.ctx.adagrad_step(m.P[:m.n_train] if m.n_train < m.P.numel() else m.P, m.G,
-                              self.hs, m.seg_off, m.seg_reg, self._hyper,
-                              **self._grad_scaling(plan))
+    _state = (('h', 'hs'),)
+    _launch = 'adagrad_step'
 
     def clear_last_dir(self):
-        """h and t back to zero: the next step is a first step again (the resettable part of
-        optimiser.py:217-220)"""
-        if self.hs is not None:
-            self.hs.zero_()
+        """h and t back to zero, a parked state dropped: the next step is a first step again (the
+        resettable part of optimiser.py:217-220)"""
+        self._zero_state()
         self._pending = None
         self._load_t(dict(t=0.0))
-
-    def state_dict(self):
-        if self.hs is None:
-            # loaded but not stepped yet: hand the parked state on (load -> save -> load)
-            if self._pending is not None and 'h' in self._pending:
-                return {'h': np.array(self._pending['h'], dtype=np.float32), 't': np.array(self.t)}
-            return {}
-        return {'h': self.hs.cpu().numpy(), 't': np.array(self.t)}
-
-    def _apply(self, d):
-        import torch
-        if 'h' in d:
-            v = np.ascontiguousarray(d['h'], dtype=np.float32)
-            if v.size != self.hs.numel():
-                raise ValueError("AdaGrad state of %i elements does not fit this model (%i)"
-                                 % (v.size, self.hs.numel()))
-            self.hs.copy_(torch.from_numpy(v))
-
-    def load_state_dict(self, d):
-        """h and the step counter t; a state loaded before the first step is kept and applied
-        when the buffers exist, so a resumed run does not double its first gradient again"""
-        if self.hs is None:
-            self._pending = {k: d[k] for k in ('h',) if k in d} or None
-        else:
-            self._apply(d)
-        self._load_t(d)
 
 
 class AdaDelta(Optimiser):
@@ -413,58 +350,11 @@ class AdaDelta(Optimiser):
     d' = mom*d + (1-mom)*dir^2 ; p' = p - lr*(dir + wd*p [*apply_reg])  (optimiser.py:222-264),
     eps = 1e-5."""
     step_name = 'AdaDelta'
-
-    def __init__(self, *a):
-        self.squared_accum = None
-        self.delta_accum = None
-        self._pending = None
-        super(AdaDelta, self).__init__(*a)
-
-    def _ensure_state(self, plan):
-        if self.squared_accum is None:
-            n = max(self.model.n_train, 4)
-            self.squared_accum = plan.zeros_flat(n)
-            self.delta_accum = plan.zeros_flat(n)
-        if self._pending is not None:
-            self._apply(self._pending)
-            self._pending = None
-
-    def device_update(self, plan):
-        m = self.model
-        plan.ctx.adadelta_step(m.P[:m.n_train] if m.n_train < m.P.numel() else m.P, m.G,
-                               self.squared_accum, self.delta_accum, m.seg_off, m.seg_reg,
-                               self._hyper, **self._grad_scaling(plan))
+    _state = (('s', 'squared_accum'), ('d', 'delta_accum'))
+    _launch = 'adadelta_step'
 
     def clear_last_dir(self):
-        """both accumulators back to zero (the resettable part of optimiser.py:267-269)"""
-        if self.squared_accum is not None:
-            self.squared_accum.zero_()
-            self.delta_accum.zero_()
+        """both accumulators back to zero, a parked state dropped (the resettable part of
+        optimiser.py:267-269)"""
+        self._zero_state()
         self._pending = None
-
-    def state_dict(self):
-        if self.squared_accum is None:
-            if self._pending is not None and 's' in self._pending:
-                return {'s': np.array(self._pending['s'], dtype=np.float32),
-                        'd': np.array(self._pending['d'], dtype=np.float32)}
-            return {}
-        return {'s': self.squared_accum.cpu().numpy(), 'd': self.delta_accum.cpu().numpy()}
-
-    def _apply(self, d):
-        import torch
-        if 's' in d:
-            s = np.ascontiguousarray(d['s'], dtype=np.float32)
-            dl = np.ascontiguousarray(d['d'], dtype=np.float32)
-            if s.size != self.squared_accum.numel() or dl.size != self.squared_accum.numel():
-                raise ValueError("AdaDelta state of %i elements does not fit this model (%i)"
-                                 % (s.size, self.squared_accum.numel()))
-            self.squared_accum.copy_(torch.from_numpy(s))
-            self.delta_accum.copy_(torch.from_numpy(dl))
-
-    def load_state_dict(self, d):
-        """both accumulators; a state loaded before the first step is kept and applied when the
-        buffers exist"""
-        if self.squared_accum is None:
-            self._pending = {k: d[k] for k in ('s', 'd') if k in d} or None
-        else:
-            self._apply(d)

@@ -13,7 +13,8 @@ import torch
 import test_optimiser_host as H
 import test_adaptive_optimisers_host as A
 from test_optimiser_host import CASES, CASE_IDS
-from test_optimiser_gpu import GRAD_NOISE, dev, host, same_bits, cus, hyper_dev, upload, check_gradient_arena, _flat_state
+from test_optimiser_gpu import GRAD_NOISE, dev, host, same_bits, cus, hyper_dev, upload, check_gradient_arena, _flat_state, \
+    check_tail_repeats_the_vector_body
 
 pytestmark = pytest.mark.gpu
 
@@ -110,6 +111,15 @@ def test_adadelta_step_against_the_restatement(ctx, idx):
     check_gradient_arena(G, c, CASE_IDS[idx])
     for store in (Ps, Gs, Ss, Ds):
         assert guards_intact(store, c['n'])
+
+
+@pytest.mark.parametrize("kernel", ["adagrad", "adadelta"])
+def test_the_scalar_tail_runs_the_rule_of_the_vector_body(ctx, kernel):
+    """tests/test_optimiser_gpu.py check_tail_repeats_the_vector_body; element 1 has no gradient on
+    h = 0 (AdaGrad leaves it as it is), element 2 none on h > 0"""
+    st = A.draw_state(np.random.RandomState(55), 4 * 256 + 3, 1.0)
+    check_tail_repeats_the_vector_body(getattr(ctx, kernel + '_step'), st,
+                                       dict(adagrad=['hs'], adadelta=['s', 'd'])[kernel])
 
 
 # ---- B. steps in a row, eager and replayed -----------------------------------------------------------

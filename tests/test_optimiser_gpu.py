@@ -122,6 +122,37 @@ def test_sgd_step_against_the_restatement(ctx, idx):
     check_gradient_arena(G, c, CASE_IDS[idx])
 
 
+def check_tail_repeats_the_vector_body(launch, st, keys):
+    """an arena of 4 * 256 + 3 elements, ONE segment with the multiplier 2.5, whose last three
+    elements repeat p, g and the state of elements 0..2: after one step the three elements of the
+    scalar tail carry the same BITS as elements 0..2 of the float4 body in every output (p and each
+    state array ``keys`` of ``st``) -- with gmul 1 and 0.5, zero_g off and on, t0 = 0 and 3.
+    ``launch``: the context's step method."""
+    n = 4 * 256 + 3
+    vals = dict((k, np.array(st[k][:n])) for k in ['p', 'g'] + list(keys))
+    for v in vals.values():
+        v[-3:] = v[:3]
+    so, sr = torch.tensor([0, n], device="cuda"), dev([2.5])
+    for gmul in (1.0, 0.5):
+        for zero_g in (False, True):
+            for t0 in (0, 3):
+                what = (gmul, zero_g, t0)
+                P, G = dev(vals['p']), dev(vals['g'])
+                S = [dev(vals[k]) for k in keys]
+                launch(P, G, *S, so, sr, hyper_dev(H.HYPERS[0], t0), gmul=gmul, zero_g=zero_g)
+                torch.cuda.synchronize()
+                assert not same_bits(P[:3], dev(vals['p'][:3])), what          # the step ran
+                for out in [P] + S:
+                    assert same_bits(out[-3:], out[:3]), what
+                assert (not G.any()) if zero_g else same_bits(G, dev(vals['g'])), what
+
+
+@pytest.mark.parametrize("kernel", ["adam", "sgd"])
+def test_the_scalar_tail_runs_the_rule_of_the_vector_body(ctx, kernel):
+    st = H.draw_state(np.random.RandomState(35), 4 * 256 + 3)
+    check_tail_repeats_the_vector_body(getattr(ctx, kernel + '_step'), st, dict(adam='ms', sgd='d')[kernel])
+
+
 # ---- B. steps in a row, eager and replayed -----------------------------------------------------------
 def _chain_case(seed, t0):
     n = H.length('wrap', 3, cus())
