@@ -69,6 +69,21 @@ __device__ __forceinline__ f32x4 pg_load(const float* row, int k, int K) {
   return v;
 }
 
+// where dw keeps element (m, n): at p.c[row + (long)n * cs], row returned (UpConv, R > 1: row
+// m = co * R + r lies at dw[co][n][r]).  Per ROW: a flush divides once per row, not per element
+__device__ __forceinline__ long pg_dw_row(const PgP& p, int m, int& cs) {
+  if (p.R > 1) { const int co = m / p.R; cs = p.R; return (long)co * p.Ncol * p.R + (m - co * p.R); }
+  cs = 1;
+  return (long)m * p.Ncol;
+}
+// ... and the same rule per ELEMENT, for the flushes that walk a tile element by element (they
+// keep the stride a constant of each branch: through pg_dw_row it is a variable, 8 instructions
+// more per flush loop in all 64 instances)
+__device__ __forceinline__ float* pg_dw(const PgP& p, int m, int n) {
+  if (p.R > 1) { const int co = m / p.R; return p.c + (long)co * p.Ncol * p.R + (m - co * p.R) + (long)n * p.R; }
+  return p.c + (long)m * p.Ncol + n;
+}
+
 // ---- f32 products from six bf16 MFMAs ("MT,NT,18,..." / "MT,NT,19,...", DESIGN.md finding 60) ----
 // An f32 value is EXACTLY hi + mid + lo, three bf16 pieces of 8 + 8 + 8 mantissa bits: hi = the top
 // 16 bits of x (truncated, so hi never rounds up to inf), r1 = x - hi (exact), mid = the top 16
@@ -192,10 +207,8 @@ __global__ __launch_bounds__(256) void pw_wgrad_kernel(PgP p) {
     for (int r = 0; r < 4; ++r) {
       const int m = m0 + 16 * mb + 4 * q + r;
       if (m >= p.M) continue;
-      long rbase;
       int cstride;
-      if (p.R > 1) { const int co = m / p.R; rbase = (long)co * p.Ncol * p.R + (m - co * p.R); cstride = p.R; }
-      else { rbase = (long)m * p.Ncol; cstride = 1; }
+      const long rbase = pg_dw_row(p, m, cstride);
 #pragma unroll
       for (int nb = 0; nb < NT; ++nb) {
         const int n = n0 + 16 * nb + l15;
@@ -218,6 +231,44 @@ __global__ __launch_bounds__(256) void pw_wgrad_kernel(PgP p) {
 // float4 of the NEXT unit are requested right after block mb's MFMAs of this unit, so every
 // load has a whole unit (13 x 2 x 8 MFMAs = 2.8 us) to arrive -- B double-buffered.  Units are
 // WHOLE; the K % 32 last positions of the samples are a masked step of the last range's work-groups.
+// pw_wgrad_ks_kernel and pw_wgrad_ev_kernel share pg_where / pg_bo / pg_load2, pg_six_units, pg_dw
+// and PgRed; their row offsets, f32 unit loop, masked step, LDS store and sum are the same text TWICE
+// (DESIGN.md finding 62: as functions each of them changes the kernels' instruction streams, and
+// the build that shared them all was 1-4 % slower per kernel) -- change both, the test
+// test_split_and_even_kernels_same_bits_* compares their bits.
+
+// What the unit loops of both kernels below, f32 and six-product, address and load with:
+// unit u (WHOLE 32-position units only): sample bases and byte offset kb of the unit inside a row
+// (TAPS: units of a PLANE; zb = byte offset of the plane inside the sample's x.  A unit may run
+// past the end of its plane: dy holds zeros there -- its border -- and x whatever follows, up to
+// 124 bytes behind the tensor for the last plane of the last channel: e2_set_input_slack)
+template <bool TAPS>
+__device__ __forceinline__ void pg_where(const PgP& p, int u, const char*& ap, const char*& bp, unsigned& kb, unsigned& zb) {
+  const int pl = u / p.stepsPerSample;
+  kb = (unsigned)(u - pl * p.stepsPerSample) * 128u;
+  if (TAPS) {
+    const int n = pl / p.planes, z = pl - n * p.planes;
+    ap = reinterpret_cast<const char*>(p.a + (long)n * p.asN + (long)z * p.asZ);
+    bp = reinterpret_cast<const char*>(p.b + (long)n * p.bsN);
+    zb = (unsigned)(z * p.bsZ) * 4u;
+  } else {
+    ap = reinterpret_cast<const char*>(p.a + (long)pl * p.asN);
+    bp = reinterpret_cast<const char*>(p.b + (long)pl * p.bsN);
+    zb = 0;
+  }
+}
+// byte offset of a unit in a row of x: the lane's row (with its tap's shift), the plane, the unit
+template <bool TAPS>
+__device__ __forceinline__ unsigned pg_bo(unsigned boff, unsigned kb, unsigned zb) {
+  return TAPS ? boff + zb + kb : boff + kb;
+}
+// lane's two float4 of a unit: a load is "scalar sample base + vector offset"
+__device__ __forceinline__ void pg_load2(f32x4 (&d)[2], const char* base, unsigned off) {
+  const char* r = base + off;                        // (4-byte aligned only: rows need not be 16-byte aligned)
+  __builtin_memcpy(&d[0], r, 16);
+  __builtin_memcpy(&d[1], r + 64, 16);
+}
+
 // The unit loop of both kernels below in the six-product form: this wave's units u0, u0 + 4, ...
 // (cnt > 0 of them) into acc.  B is split ONCE per unit and its pieces serve all MT blocks; A is
 // split per block, block mb + 1's split next to block mb's MFMAs (one wave per SIMD: the shadow of
@@ -227,46 +278,23 @@ __global__ __launch_bounds__(256) void pw_wgrad_kernel(PgP p) {
 template <int MT, int NT, bool TAPS>
 __device__ __forceinline__ void pg_six_units(const PgP& p, int u0, int cnt, const unsigned (&aoff)[MT],
                                              const unsigned (&boff)[NT], f32x4 (&acc)[MT][NT]) {
-  auto where = [&](int i, const char*& ap, const char*& bp, unsigned& kb, unsigned& zb) {
-    const int u = u0 + 4 * i;
-    const int pl = u / p.stepsPerSample;
-    kb = (unsigned)(u - pl * p.stepsPerSample) * 128u;
-    if (TAPS) {
-      const int n = pl / p.planes, z = pl - n * p.planes;
-      ap = reinterpret_cast<const char*>(p.a + (long)n * p.asN + (long)z * p.asZ);
-      bp = reinterpret_cast<const char*>(p.b + (long)n * p.bsN);
-      zb = (unsigned)(z * p.bsZ) * 4u;
-    } else {
-      ap = reinterpret_cast<const char*>(p.a + (long)pl * p.asN);
-      bp = reinterpret_cast<const char*>(p.b + (long)pl * p.bsN);
-      zb = 0;
-    }
-  };
-  auto bo = [&](int nb, unsigned kb, unsigned zb) -> unsigned {
-    return TAPS ? boff[nb] + zb + kb : boff[nb] + kb;
-  };
-  auto load2 = [&](f32x4 (&d)[2], const char* base, unsigned off) {
-    const char* r = base + off;                      // (4-byte aligned only)
-    __builtin_memcpy(&d[0], r, 16);
-    __builtin_memcpy(&d[1], r + 64, 16);
-  };
   f32x4 A[MT][2], Bn[NT][2];
   Pc3 Ap, Bp[NT];
   const char *ap, *bp;
   unsigned kb, zb;
-  where(0, ap, bp, kb, zb);
+  pg_where<TAPS>(p, u0, ap, bp, kb, zb);
 #pragma unroll
-  for (int nb = 0; nb < NT; ++nb) load2(Bn[nb], bp, bo(nb, kb, zb));
+  for (int nb = 0; nb < NT; ++nb) pg_load2(Bn[nb], bp, pg_bo<TAPS>(boff[nb], kb, zb));
 #pragma unroll
-  for (int mb = 0; mb < MT; ++mb) load2(A[mb], ap, aoff[mb] + kb);
+  for (int mb = 0; mb < MT; ++mb) pg_load2(A[mb], ap, aoff[mb] + kb);
 #pragma unroll
   for (int nb = 0; nb < NT; ++nb) Bp[nb] = pg_split8(Bn[nb]);
   Ap = pg_split8(A[0]);
   // (the last trips request their own unit again: L1 / L2 hits, nothing waits for them)
-  where(min(1, cnt - 1), ap, bp, kb, zb);
+  pg_where<TAPS>(p, u0 + 4 * min(1, cnt - 1), ap, bp, kb, zb);
 #pragma unroll
-  for (int nb = 0; nb < NT; ++nb) load2(Bn[nb], bp, bo(nb, kb, zb));
-  load2(A[0], ap, aoff[0] + kb);
+  for (int nb = 0; nb < NT; ++nb) pg_load2(Bn[nb], bp, pg_bo<TAPS>(boff[nb], kb, zb));
+  pg_load2(A[0], ap, aoff[0] + kb);
   // ONE loop body (accumulators stay where they are); (ap, kb) = where unit i + 1 is
 #pragma unroll 1
   for (int i = 0; i < cnt; ++i) {
@@ -276,15 +304,15 @@ __device__ __forceinline__ void pg_six_units(const PgP& p, int u0, int cnt, cons
       Pc3 An;
       if (mb + 1 < MT) {
         An = pg_split8(A[mb + 1]);
-        load2(A[mb + 1], ap, aoff[mb + 1] + kb);
+        pg_load2(A[mb + 1], ap, aoff[mb + 1] + kb);
       } else {
         An = pg_split8(A[0]);
 #pragma unroll
         for (int nb = 0; nb < NT; ++nb) Bq[nb] = pg_split8(Bn[nb]);
-        where(min(i + 2, cnt - 1), ap, bp, kb, zb);
+        pg_where<TAPS>(p, u0 + 4 * min(i + 2, cnt - 1), ap, bp, kb, zb);
 #pragma unroll
-        for (int nb = 0; nb < NT; ++nb) load2(Bn[nb], bp, bo(nb, kb, zb));
-        load2(A[0], ap, aoff[0] + kb);
+        for (int nb = 0; nb < NT; ++nb) pg_load2(Bn[nb], bp, pg_bo<TAPS>(boff[nb], kb, zb));
+        pg_load2(A[0], ap, aoff[0] + kb);
       }
       pg_mfma6<NT>(Ap, Bp, acc[mb]);
       Ap = An;
@@ -295,11 +323,18 @@ __device__ __forceinline__ void pg_six_units(const PgP& p, int u0, int cnt, cons
   }
 }
 
+// the LDS in which both kernels below sum the four waves' partial tiles (and what their launchers ask for)
+template <int MT, int NT>
+struct PgRed {
+  static constexpr int RW = 16 * NT + 4;             // padded row of a wave's partial tile
+  static constexpr int RS = 16 * MT * RW;            // one wave's partial tile
+  static constexpr int BYTES = 4 * RS * (int)sizeof(float);
+};
+
 template <int MT, int NT, bool TAPS, bool SIX = false>
 __global__ __launch_bounds__(256) void pw_wgrad_ks_kernel(PgP p) {
   extern __shared__ float red[];
-  constexpr int RW = 16 * NT + 4;                    // padded row of a wave's partial tile
-  constexpr int RS = 16 * MT * RW;
+  constexpr int RW = PgRed<MT, NT>::RW, RS = PgRed<MT, NT>::RS;
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, q = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // work-groups b, b + 8, b + 16 ... share an XCD: the tiles of one position range are
@@ -311,10 +346,6 @@ __global__ __launch_bounds__(256) void pw_wgrad_ks_kernel(PgP p) {
   const int sp = L / p.nMT;
   const int m0 = mt * 16 * MT, n0 = nt * 16 * NT;
   const bool single = p.S == 1;
-  auto dst_of = [&](int m, int n) -> float* {
-    if (p.R > 1) { const int co = m / p.R; return p.c + (long)co * p.Ncol * p.R + (m - co * p.R) + (long)n * p.R; }
-    return p.c + (long)m * p.Ncol + n;
-  };
 
   if (sp >= p.S) return;                             // (grid padded to a multiple of 8)
   const int u0 = sp * p.per + wave, u1 = min(sp * p.per + p.per, p.steps);
@@ -348,53 +379,25 @@ __global__ __launch_bounds__(256) void pw_wgrad_ks_kernel(PgP p) {
 #pragma unroll
     for (int nb = 0; nb < NT; ++nb) acc[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // unit i of this wave (WHOLE 32-position units only): sample bases and byte offset of the unit
-  // (TAPS: units of a PLANE; zb = byte offset of the plane inside the sample's x.  A unit may run
-  // past the end of its plane: dy holds zeros there -- its border -- and x whatever follows, up to
-  // 124 bytes behind the tensor for the last plane of the last channel: e2_set_input_slack)
-  auto where = [&](int i, const char*& ap, const char*& bp, unsigned& kb, unsigned& zb) {
-    const int u = u0 + 4 * i;
-    const int pl = u / p.stepsPerSample;
-    kb = (unsigned)(u - pl * p.stepsPerSample) * 128u;
-    if (TAPS) {
-      const int n = pl / p.planes, z = pl - n * p.planes;
-      ap = reinterpret_cast<const char*>(p.a + (long)n * p.asN + (long)z * p.asZ);
-      bp = reinterpret_cast<const char*>(p.b + (long)n * p.bsN);
-      zb = (unsigned)(z * p.bsZ) * 4u;
-    } else {
-      ap = reinterpret_cast<const char*>(p.a + (long)pl * p.asN);
-      bp = reinterpret_cast<const char*>(p.b + (long)pl * p.bsN);
-      zb = 0;
-    }
-  };
-  auto bo = [&](int nb, unsigned kb, unsigned zb) -> unsigned {
-    return TAPS ? boff[nb] + zb + kb : boff[nb] + kb;
-  };
-  auto load2 = [&](f32x4 (&d)[2], const char* base, unsigned off) {
-    const char* r = base + off;                      // (4-byte aligned only: rows need not be 16-byte aligned)
-    __builtin_memcpy(&d[0], r, 16);
-    __builtin_memcpy(&d[1], r + 64, 16);
-  };
-
   if constexpr (SIX) {
     if (cnt > 0) pg_six_units<MT, NT, TAPS>(p, u0, cnt, aoff, boff, acc);
   } else if (cnt > 0) {
     f32x4 A[MT][2], Bc[NT][2], Bn[NT][2];
     const char *ap, *bp;
     unsigned kb, zb;
-    where(0, ap, bp, kb, zb);
+    pg_where<TAPS>(p, u0, ap, bp, kb, zb);
 #pragma unroll
-    for (int nb = 0; nb < NT; ++nb) load2(Bc[nb], bp, bo(nb, kb, zb));
+    for (int nb = 0; nb < NT; ++nb) pg_load2(Bc[nb], bp, pg_bo<TAPS>(boff[nb], kb, zb));
 #pragma unroll
-    for (int mb = 0; mb < MT; ++mb) load2(A[mb], ap, aoff[mb] + kb);
+    for (int mb = 0; mb < MT; ++mb) pg_load2(A[mb], ap, aoff[mb] + kb);
     KS_STAMP(1);
     // ONE loop body (accumulators stay where they are): the last trip requests its own unit
     // again -- L1 / L2 hits, nothing waits for them
 #pragma unroll 1
     for (int i = 0; i < cnt; ++i) {
-      where(min(i + 1, cnt - 1), ap, bp, kb, zb);
+      pg_where<TAPS>(p, u0 + 4 * min(i + 1, cnt - 1), ap, bp, kb, zb);
 #pragma unroll
-      for (int nb = 0; nb < NT; ++nb) load2(Bn[nb], bp, bo(nb, kb, zb));
+      for (int nb = 0; nb < NT; ++nb) pg_load2(Bn[nb], bp, pg_bo<TAPS>(boff[nb], kb, zb));
 #pragma unroll
       for (int mb = 0; mb < MT; ++mb) {
 #pragma unroll
@@ -404,7 +407,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_ks_kernel(PgP p) {
 #pragma unroll
             for (int nb = 0; nb < NT; ++nb)
               acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[mb][h][j], Bc[nb][h][j], acc[mb][nb], 0, 0, 0);
-        load2(A[mb], ap, aoff[mb] + kb);
+        pg_load2(A[mb], ap, aoff[mb] + kb);
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
@@ -467,7 +470,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_ks_kernel(PgP p) {
     const float* s = red + ml * RW + nl;
     const float v = (s[0] + s[RS]) + (s[2 * RS] + s[3 * RS]);
     if (m >= p.M || n >= p.Ncol) continue;
-    float* dst = dst_of(m, n);
+    float* dst = pg_dw(p, m, n);
     if (single) *dst += v;                           // (dw was zeroed or holds what to add to)
     else unsafeAtomicAdd(dst, v);
   }
@@ -482,13 +485,12 @@ __global__ __launch_bounds__(256) void pw_wgrad_ks_kernel(PgP p) {
 // CUs x residency (57 tiles x 4 = 228 work-groups for 256 CUs).  Here G work-groups share the
 // tiles x units pairs evenly (wgrad_even.hpp); a work-group whose range crosses a tile boundary
 // runs one segment per tile -- zero, multiply, sum through LDS, flush with atomics -- so a tile
-// has any number of producers.  A kernel of its own: pw_wgrad_ks_kernel keeps its instruction
-// stream.  The segment loop has ONE exit and is never unrolled (DESIGN.md lessons 5 and 10).
+// has any number of producers.  A kernel of its own, the tile's body copied from
+// pw_wgrad_ks_kernel (see above): that kernel keeps its instruction stream.  The segment loop has ONE exit and is never unrolled (DESIGN.md lessons 5 and 10).
 template <int MT, int NT, bool TAPS, bool SIX = false>
 __global__ __launch_bounds__(256) void pw_wgrad_ev_kernel(PgP p, WgEven ev) {
   extern __shared__ float red[];
-  constexpr int RW = 16 * NT + 4;                    // padded row of a wave's partial tile
-  constexpr int RS = 16 * MT * RW;
+  constexpr int RW = PgRed<MT, NT>::RW, RS = PgRed<MT, NT>::RS;
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, q = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // work-groups b, b + 8, b + 16 ... share an XCD: consecutive ranges -- the tiles of one band of
@@ -534,48 +536,23 @@ __global__ __launch_bounds__(256) void pw_wgrad_ev_kernel(PgP p, WgEven ev) {
 #pragma unroll
       for (int nb = 0; nb < NT; ++nb) acc[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // unit i of this wave in this segment (see pw_wgrad_ks_kernel: whole units, TAPS: of a plane)
-    auto where = [&](int i, const char*& ap, const char*& bp, unsigned& kb, unsigned& zb) {
-      const int u = u0 + 4 * i;
-      const int pl = u / p.stepsPerSample;
-      kb = (unsigned)(u - pl * p.stepsPerSample) * 128u;
-      if (TAPS) {
-        const int n = pl / p.planes, z = pl - n * p.planes;
-        ap = reinterpret_cast<const char*>(p.a + (long)n * p.asN + (long)z * p.asZ);
-        bp = reinterpret_cast<const char*>(p.b + (long)n * p.bsN);
-        zb = (unsigned)(z * p.bsZ) * 4u;
-      } else {
-        ap = reinterpret_cast<const char*>(p.a + (long)pl * p.asN);
-        bp = reinterpret_cast<const char*>(p.b + (long)pl * p.bsN);
-        zb = 0;
-      }
-    };
-    auto bo = [&](int nb, unsigned kb, unsigned zb) -> unsigned {
-      return TAPS ? boff[nb] + zb + kb : boff[nb] + kb;
-    };
-    auto load2 = [&](f32x4 (&d)[2], const char* base, unsigned off) {
-      const char* r = base + off;                    // (4-byte aligned only)
-      __builtin_memcpy(&d[0], r, 16);
-      __builtin_memcpy(&d[1], r + 64, 16);
-    };
-
     if constexpr (SIX) {
       if (cnt > 0) pg_six_units<MT, NT, TAPS>(p, u0, cnt, aoff, boff, acc);
     } else if (cnt > 0) {
       f32x4 A[MT][2], Bc[NT][2], Bn[NT][2];
       const char *ap, *bp;
       unsigned kb, zb;
-      where(0, ap, bp, kb, zb);
+      pg_where<TAPS>(p, u0, ap, bp, kb, zb);
 #pragma unroll
-      for (int nb = 0; nb < NT; ++nb) load2(Bc[nb], bp, bo(nb, kb, zb));
+      for (int nb = 0; nb < NT; ++nb) pg_load2(Bc[nb], bp, pg_bo<TAPS>(boff[nb], kb, zb));
 #pragma unroll
-      for (int mb = 0; mb < MT; ++mb) load2(A[mb], ap, aoff[mb] + kb);
+      for (int mb = 0; mb < MT; ++mb) pg_load2(A[mb], ap, aoff[mb] + kb);
       // ONE loop body; the last trip requests its own unit again (L1 / L2 hits, nothing waits)
 #pragma unroll 1
       for (int i = 0; i < cnt; ++i) {
-        where(min(i + 1, cnt - 1), ap, bp, kb, zb);
+        pg_where<TAPS>(p, u0 + 4 * min(i + 1, cnt - 1), ap, bp, kb, zb);
 #pragma unroll
-        for (int nb = 0; nb < NT; ++nb) load2(Bn[nb], bp, bo(nb, kb, zb));
+        for (int nb = 0; nb < NT; ++nb) pg_load2(Bn[nb], bp, pg_bo<TAPS>(boff[nb], kb, zb));
 #pragma unroll
         for (int mb = 0; mb < MT; ++mb) {
 #pragma unroll
@@ -585,7 +562,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_ev_kernel(PgP p, WgEven ev) {
 #pragma unroll
               for (int nb = 0; nb < NT; ++nb)
                 acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[mb][h][j], Bc[nb][h][j], acc[mb][nb], 0, 0, 0);
-          load2(A[mb], ap, aoff[mb] + kb);
+          pg_load2(A[mb], ap, aoff[mb] + kb);
           __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
@@ -642,10 +619,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_ev_kernel(PgP p, WgEven ev) {
       const float* s = red + ml * RW + nl;
       const float v = (s[0] + s[RS]) + (s[2 * RS] + s[3 * RS]);
       if (m >= p.M || n >= p.Ncol) continue;
-      float* dst;
-      if (p.R > 1) { const int co = m / p.R; dst = p.c + (long)co * p.Ncol * p.R + (m - co * p.R) + (long)n * p.R; }
-      else dst = p.c + (long)m * p.Ncol + n;
-      unsafeAtomicAdd(dst, v);
+      unsafeAtomicAdd(pg_dw(p, m, n), v);
     }
     __syncthreads();                                 // (the next segment writes `red` again)
 #ifdef E2_DEBUG_ENV
@@ -665,7 +639,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_ev_kernel(PgP p, WgEven ev) {
 
 template <int MT, int NT, bool TAPS, bool SIX>
 int launch_ev(e2_ctx* ctx, const PgP& p, const WgEven& ev) {
-  const int lds = 4 * 16 * MT * (16 * NT + 4) * (int)sizeof(float);
+  constexpr int lds = PgRed<MT, NT>::BYTES;
   static bool raised = false;
   if (int rc = e2i_raise_lds(reinterpret_cast<const void*>(&pw_wgrad_ev_kernel<MT, NT, TAPS, SIX>), lds, &raised)) return rc;
   PgP ps = p;
@@ -721,7 +695,7 @@ static int even_split(const PgP& p, long G, int B, WgEven* ev) {
 
 template <int MT, int NT, bool TAPS, bool SIX>
 int launch_ks(e2_ctx* ctx, const PgP& p, long grid) {
-  const int lds = 4 * 16 * MT * (16 * NT + 4) * (int)sizeof(float);
+  constexpr int lds = PgRed<MT, NT>::BYTES;
   static bool raised = false;
   if (int rc = e2i_raise_lds(reinterpret_cast<const void*>(&pw_wgrad_ks_kernel<MT, NT, TAPS, SIX>), lds, &raised)) return rc;
 #ifdef E2_DEBUG_ENV

@@ -89,6 +89,73 @@ def test_pointwise_wgrad_even_ranges(ctx, force):
         ctx.set_tiling("wgrad", None)
 
 
+def _single_producer(tile, form, rows, cols):
+    """the three tilings that give every tile ONE producer: the position split with S = 1, even
+    ranges with one work-group walking every tile, even ranges with one work-group per tile"""
+    mt, nt = (int(v) for v in tile.split(","))
+    tiles = -(-rows // (16 * mt)) * -(-cols // (16 * nt))
+    return ["%s,%d,0,1" % (tile, form), "%s,%d,1,1" % (tile, form), "%s,%d,1,%d" % (tile, form, tiles)]
+
+
+def _assert_same_bits(ctx, forces, launch, run, ref):
+    """pw_wgrad_ks_kernel and pw_wgrad_ev_kernel are two hand-kept copies of one tile body
+    (DESIGN.md finding 62); this pins them to each other: with one producer per tile a wave gets
+    the same units in the same order and the sums are added to a zeroed dw, so the results are
+    EQUAL, first write and accumulate -- no tolerance"""
+    got = []
+    try:
+        for force in forces:
+            ctx.set_tiling("wgrad", force)
+            dw = torch.full(ref.shape, float("nan"), device="cuda")
+            run(dw, False)
+            assert ctx.last_launch() == (launch, force, "forced")
+            first = dw.clone()
+            run(dw, True)
+            assert ctx.last_launch() == (launch, force, "forced")
+            got.append((first, dw))
+    finally:
+        ctx.set_tiling("wgrad", None)
+    assert relerr(got[0][0], ref) < TOL and relerr(got[0][1], 2 * ref) < TOL
+    for force, (first, second) in zip(forces[1:], got[1:]):
+        assert torch.equal(first, got[0][0]), force
+        assert torch.equal(second, got[0][1]), force + " (accumulate)"
+
+
+@pytest.mark.parametrize("form", [9, 19])
+@pytest.mark.parametrize("tile", ["7,2", "13,2", "2,4"])
+def test_split_and_even_kernels_same_bits_with_taps(ctx, tile, form):
+    """both unit loops (f32 and six products), 6 / 6 / 12 tiles"""
+    ci, co, k, sp = PROBLEMS[2]
+    x, dy, dw_ref = problem(ci, co, k, sp)
+    dyp = _plan_style_padded(dy, k)
+    xflat = torch.full((x.size + 32,), 1e30, device="cuda")
+    xd = xflat[:x.size].view(x.shape)
+    xd.copy_(dev(x))
+    ctx.set_input_slack(128)
+    try:
+        _assert_same_bits(ctx, _single_producer(tile, form, co, ci * int(np.prod(k))), "wgrad_ks",
+                          lambda dw, acc: ctx.conv3d_wgrad_pad(xd, dyp, dw, accumulate=acc), dw_ref)
+    finally:
+        ctx.set_input_slack(0)
+
+
+@pytest.mark.parametrize("form", [8, 18])
+def test_split_and_even_kernels_same_bits_pointwise(ctx, form):
+    """the 1x1x1 form of test_pointwise_wgrad_even_ranges: K % 32 = 17, so the masked step runs,
+    in the work-group of the last range there and in the segment with the last unit here; 3 tiles"""
+    Ci, Co, sp = 70, 100, (3, 7, 13)
+    rng = np.random.RandomState(Ci + Co)
+    x = rng.rand(N, Ci, *sp).astype(np.float32)
+    dy = rng.randn(N, Co, *sp).astype(np.float32)
+    ref = O.conv3d_wgrad(dy, x, (Co, Ci, 1, 1, 1))
+    flat = torch.zeros(dy.size + 32, device="cuda")
+    dyp = flat[:dy.size].view(dy.shape)
+    dyp.copy_(dev(dy))
+    xd = dev(x)
+    _assert_same_bits(ctx, _single_producer("7,2", form, Co, Ci), "pw_wgrad_ks",
+                      lambda dw, acc: ctx.conv3d_wgrad_pad(xd, dyp, dw, accumulate=acc), ref)
+
+
 @pytest.mark.parametrize("force", ["7,2,9,1,0", "7,2,9,1,65537", "7,2,9,100000,37"])
 def test_even_ranges_out_of_range_are_refused(ctx, force):
     """e2_last_launch reports the string that ran: a work-group count outside 1 .. 65536 or more
