@@ -250,6 +250,15 @@ def _load():
         "e2_loss_mix": (C.c_int, [vp, i, PL, C.POINTER(C.c_void_p), C.POINTER(sz),
                                   C.POINTER(C.c_int64), fp, fp, fp, fp, fp]),
         "e2_loss_bwd": (C.c_int, [vp, PL, P5, P5, P5, fp, P5, P5, i]),
+        "e2_fdist_fwd": (C.c_int, [vp, P5, P5, P5]),
+        "e2_fdist_bwd": (C.c_int, [vp, P5, P5, P5, P5, P5, P5, i, i]),
+        "e2_ramp_fwd": (C.c_int, [vp, P5, P5, fp, P5]),
+        "e2_ramp_bwd": (C.c_int, [vp, P5, P5, fp, P5, P5, P5, i, i]),
+        "e2_mean_fwd": (C.c_int, [vp, P5, fp]),
+        "e2_mean_bwd": (C.c_int, [vp, fp, P5, i]),
+        "e2_onehot": (C.c_int, [vp, P5, i, P5]),
+        "e2_beta_nll_fwd": (C.c_int, [vp, P5, P5, P5, fp]),
+        "e2_beta_nll_bwd": (C.c_int, [vp, P5, P5, P5, fp, P5, P5, i]),
         "e2_adam_step": (C.c_int, [vp, fp, fp, fp, fp, sz, vp, fp, i, fp]),
         "e2_sgd_step": (C.c_int, [vp, fp, fp, fp, sz, vp, fp, i, fp]),
         "e2_set_loss_grad_mode": (C.c_int, [vp, i, fp]),
@@ -760,6 +769,62 @@ class Context:
         _chk(_lib.e2_loss_bwd(self.h, C.byref(term), C.byref(t5(pred)), opt(sig),
                               C.byref(t5(target)), _fp(coef), opt(dpred), opt(dsig),
                               int(bool(accumulate))), "e2_loss_bwd")
+
+    # ---- losses over the feature axis, the mean of a loss map (csrc/loss_map.hip) ---------------
+    def fdist_fwd(self, pred, target, out):
+        """out[n,0,...] = sqrt(sum_f (target - pred)^2), NaN stored as 0"""
+        _chk(_lib.e2_fdist_fwd(self.h, C.byref(t5(pred)), C.byref(t5(target)), C.byref(t5(out))),
+             "e2_fdist_fwd")
+
+    def fdist_bwd(self, pred, target, out, dout, dpred, dtarget=None, acc_pred=False,
+                  acc_target=False):
+        """dpred (=|+=) -(target - pred) / out * dout, dtarget the negative; either may be None"""
+        opt = lambda t: None if t is None else C.byref(t5(t))
+        _chk(_lib.e2_fdist_bwd(self.h, C.byref(t5(pred)), C.byref(t5(target)), C.byref(t5(out)),
+                               C.byref(t5(dout)), opt(dpred), opt(dtarget), int(bool(acc_pred)),
+                               int(bool(acc_target))), "e2_fdist_bwd")
+
+    def ramp_fwd(self, d_low, d_big, margin, out):
+        """out[n,0,...] = mean_f max(d_low - d_big + margin, 0), NaN as 0; ``margin``: a one-
+        element device tensor read when the kernel runs"""
+        _chk(_lib.e2_ramp_fwd(self.h, C.byref(t5(d_low)), C.byref(t5(d_big)), _fp(margin),
+                              C.byref(t5(out))), "e2_ramp_fwd")
+
+    def ramp_bwd(self, d_low, d_big, margin, dout, dd_low, dd_big=None, acc_low=False,
+                 acc_big=False):
+        opt = lambda t: None if t is None else C.byref(t5(t))
+        _chk(_lib.e2_ramp_bwd(self.h, C.byref(t5(d_low)), C.byref(t5(d_big)), _fp(margin),
+                              C.byref(t5(dout)), opt(dd_low), opt(dd_big), int(bool(acc_low)),
+                              int(bool(acc_big))), "e2_ramp_bwd")
+
+    def mean_fwd(self, x, partials):
+        """slab rows (sum x, elements, 0, 0): a term of loss_mix under a 'gauss_nll' descriptor"""
+        if partials.numel() < 4 * self.loss_partials(x):
+            raise E2Error("mean_fwd: the partials slab is too small for this tensor")
+        _chk(_lib.e2_mean_fwd(self.h, C.byref(t5(x)), _fp(partials)), "e2_mean_fwd")
+
+    def onehot(self, target, out):
+        """out[n,k,...] = (target[n,0,...] == k) as float, k < out.shape[1]; exact equality"""
+        _chk(_lib.e2_onehot(self.h, C.byref(t5(target)), int(out.shape[1]), C.byref(t5(out))),
+             "e2_onehot")
+
+    def beta_nll_fwd(self, mode, conc, target, partials):
+        """slab rows of the BetaNLL sums: a term of loss_mix under a 'gauss_nll' descriptor"""
+        if partials.numel() < 4 * self.loss_partials(mode):
+            raise E2Error("beta_nll_fwd: the partials slab is too small for this prediction")
+        _chk(_lib.e2_beta_nll_fwd(self.h, C.byref(t5(mode)), C.byref(t5(conc)),
+                                  C.byref(t5(target)), _fp(partials)), "e2_beta_nll_fwd")
+
+    def beta_nll_bwd(self, mode, conc, target, coef, dmode, dconc=None, accumulate=False):
+        opt = lambda t: None if t is None else C.byref(t5(t))
+        _chk(_lib.e2_beta_nll_bwd(self.h, C.byref(t5(mode)), C.byref(t5(conc)),
+                                  C.byref(t5(target)), _fp(coef), opt(dmode), opt(dconc),
+                                  int(bool(accumulate))), "e2_beta_nll_bwd")
+
+    def mean_bwd(self, coef, dx, accumulate=False):
+        """dx (=|+=) coef[0]; ``coef``: the one-element device tensor loss_mix wrote"""
+        _chk(_lib.e2_mean_bwd(self.h, _fp(coef), C.byref(t5(dx)), int(bool(accumulate))),
+             "e2_mean_bwd")
 
     def act_bwd(self, dout, pre, bias, act, dpre, dbias):
         """dpre = dout * f'(pre + bias[c]), dbias[c] += sum(dpre) (None: not wanted); dpre may

@@ -22,6 +22,10 @@
 // (GAUSS: w_k / (K n_tot)) and the total (1/K) sum_k w_k L_k.  The backward kernel reads its
 // coefficient, margin and scale_correction from device memory when it runs.
 //
+// BetaNLL (loss.py:890-950) runs through the same kernel templates under an internal kind with
+// entry points of its own (e2_beta_nll_fwd / e2_beta_nll_bwd, at the end of this file): the public
+// enum, e2_loss_term and e2_loss_mix do not change; in the mix it is a GAUSS_NLL-kind row.
+//
 // Geometry as in act.hip: a thread owns FOUR consecutive x of one row and moves them as one
 // 16-byte access where that piece is 16-byte aligned in every view, element by element at row ends
 // and on misaligned views; axes that are dense in all views are collapsed on the host (here also
@@ -34,6 +38,13 @@ namespace {
 #define E2_LOSS_EPS 1e-5f
 #define E2_LOSS_MASK_TOL (1e-8f + 666e-5f)
 #define E2_HALF_LOG_2PI 0.91893853320467274178f
+
+// BetaNLL runs through the same kernel templates under a kind of its own that is NOT part of the
+// public enum: e2_loss_term, e2_loss_fwd / e2_loss_bwd and e2_loss_mix do not know it (the mix
+// gets a GAUSS_NLL-kind descriptor for it: the same plain mean over n_tot)
+#define E2I_LOSS_BETA_NLL 4
+// kinds with a second prediction view (GAUSS: sigma, BETA: the concentration)
+#define E2I_TWO_PRED(KIND) ((KIND) == E2_LOSS_GAUSS_NLL || (KIND) == E2I_LOSS_BETA_NLL)
 
 typedef float loss_f4 __attribute__((ext_vector_type(4)));
 
@@ -83,10 +94,53 @@ __device__ __forceinline__ long voff(const LView& v, const Pos& q) {
 __device__ __forceinline__ bool masked(float t) { return fabsf(t + 666.0f) <= E2_LOSS_MASK_TOL; }
 __device__ __forceinline__ float xlogy0(float x, float y) { return x == 0.f ? 0.f : x * logf(y); }
 
+// psi(x) = d/dx log Gamma(x) in f32, which the device math library does not have: the recurrence
+// psi(x) = psi(x + 1) - 1/x up to an argument of at least 6 (five steps from the domain's x > 1; the
+// loop is bounded, so no argument can hold a thread), then the asymptotic series, whose first
+// dropped term is 1 / (132 x^10) < 1.3e-10 there
+__device__ __forceinline__ float digammaf(float x) {
+  float r = 0.f;
+  for (int i = 0; i < 6 && x < 6.f; ++i) {
+    r -= 1.f / x;
+    x += 1.f;
+  }
+  const float i1 = 1.f / x, i2 = i1 * i1;
+  const float ser = i2 * (1.f / 12.f - i2 * (1.f / 120.f - i2 * (1.f / 252.f - i2 * (1.f / 240.f))));
+  return r + (logf(x) - 0.5f * i1 - ser);
+}
+
+// BetaNLL (loss.py:936-950): m mode, c concentration, x target, a = m (c - 2) + 1,
+// b = (1 - m)(c - 2) + 1:
+//   l = -[lgamma(a + b) - lgamma(a) - lgamma(b) + (a - 1) log(x + EPS) + (b - 1) log(1 - x + EPS)]
+//       + softplus(-c)
+// Domain c > 2, 0 < m < 1 (a, b > 1).  Outside it the formula is followed as far as lgammaf goes;
+// nothing is guarded.
+__device__ __forceinline__ float beta_nll(float m, float c, float x) {
+  const float a = m * (c - 2.f) + 1.f, b = (1.f - m) * (c - 2.f) + 1.f;
+  const float lx = logf(x + E2_LOSS_EPS), l1x = logf(1.f - x + E2_LOSS_EPS);
+  const float p = lgammaf(a + b) - lgammaf(a) - lgammaf(b) + (a - 1.f) * lx + (b - 1.f) * l1x;
+  return -p + log1pf(expf(-c));
+}
+//   dl/dm = (c - 2) [psi(a) - psi(b) - log(x + EPS) + log(1 - x + EPS)]
+//   dl/dc = -psi(a + b) + m psi(a) + (1 - m) psi(b) - m log(x + EPS) - (1 - m) log(1 - x + EPS)
+//           - sigmoid(-c)
+__device__ __forceinline__ void beta_grad(float m, float c, float x, float& gm, float& gc) {
+  const float a = m * (c - 2.f) + 1.f, b = (1.f - m) * (c - 2.f) + 1.f;
+  const float lx = logf(x + E2_LOSS_EPS), l1x = logf(1.f - x + E2_LOSS_EPS);
+  const float pa = digammaf(a), pb = digammaf(b);
+  gm = (c - 2.f) * ((pa - pb) - lx + l1x);
+  gc = -digammaf(a + b) + m * (pa - lx) + (1.f - m) * (pb - l1x) - 1.f / (1.f + expf(c));
+}
+
 // one element of the forward sums.  FLAG: subtract_label_entropy (BINARY), sig_is_log (GAUSS)
 template <int KIND, bool MARGIN, bool SC, bool FLAG>
 __device__ __forceinline__ void fwd_elem(float pv, float sv, float tv, float m, float sc, float& s1,
                                          float& nl, float& s2) {
+  if (KIND == E2I_LOSS_BETA_NLL) {
+    s1 += beta_nll(pv, sv, tv);
+    nl += 1.f;
+    return;
+  }
   if (KIND == E2_LOSS_GAUSS_NLL) {
     const float s = FLAG ? expf(sv) : sv;
     const float ls = FLAG ? sv : logf(sv);
@@ -125,12 +179,12 @@ __global__ __launch_bounds__(256) void e2loss_fwd_kernel(LossP p) {
     const Pos q = locate(p, s);
     const float* pp = p.pred + voff(p.vp, q);
     const float* tp = p.tgt + voff(p.vt, q);
-    const float* sp = KIND == E2_LOSS_GAUSS_NLL ? p.sig + voff(p.vs, q) : pp;
+    const float* sp = E2I_TWO_PRED(KIND) ? p.sig + voff(p.vs, q) : pp;
     if (q.x0 + 4u <= p.w && ((((uintptr_t)pp) | ((uintptr_t)tp) | ((uintptr_t)sp)) & 15) == 0) {
       const loss_f4 pv = *reinterpret_cast<const loss_f4*>(pp);
       const loss_f4 tv = *reinterpret_cast<const loss_f4*>(tp);
       loss_f4 sv = pv;
-      if (KIND == E2_LOSS_GAUSS_NLL) sv = *reinterpret_cast<const loss_f4*>(sp);
+      if (E2I_TWO_PRED(KIND)) sv = *reinterpret_cast<const loss_f4*>(sp);
       fwd_elem<KIND, MARGIN, SC, FLAG>(pv[0], sv[0], tv[0], m, sc, s1, nl, s2);
       fwd_elem<KIND, MARGIN, SC, FLAG>(pv[1], sv[1], tv[1], m, sc, s1, nl, s2);
       fwd_elem<KIND, MARGIN, SC, FLAG>(pv[2], sv[2], tv[2], m, sc, s1, nl, s2);
@@ -162,6 +216,12 @@ template <int KIND, bool MARGIN, bool SC, bool FLAG>
 __device__ __forceinline__ void bwd_elem(float pv, float sv, float tv, float m, float sc, float co,
                                          float& gp, float& gs) {
   gs = 0.f;
+  if (KIND == E2I_LOSS_BETA_NLL) {
+    beta_grad(pv, sv, tv, gp, gs);
+    gp *= co;
+    gs *= co;
+    return;
+  }
   if (KIND == E2_LOSS_GAUSS_NLL) {
     const float s = FLAG ? expf(sv) : sv;
     const float z = (tv - pv) / s;
@@ -191,13 +251,13 @@ __global__ __launch_bounds__(256) void e2loss_bwd_kernel(LossP p) {
   const float m = MARGIN ? e2_uniform_ld(p.margin, 0) : 0.f;
   const float sc = SC ? e2_uniform_ld(p.sc, 0) : 0.f;
   const float co = e2_uniform_ld(p.coef, 0);
-  const bool wp = p.dpred != nullptr, ws = KIND == E2_LOSS_GAUSS_NLL && p.dsig != nullptr;
+  const bool wp = p.dpred != nullptr, ws = E2I_TWO_PRED(KIND) && p.dsig != nullptr;
   const unsigned step = gridDim.x * 256u;
   for (unsigned s = blockIdx.x * 256u + threadIdx.x; s < p.items; s += step) {
     const Pos q = locate(p, s);
     const float* pp = p.pred + voff(p.vp, q);
     const float* tp = p.tgt + voff(p.vt, q);
-    const float* sp = KIND == E2_LOSS_GAUSS_NLL ? p.sig + voff(p.vs, q) : pp;
+    const float* sp = E2I_TWO_PRED(KIND) ? p.sig + voff(p.vs, q) : pp;
     float* dp = wp ? p.dpred + voff(p.vdp, q) : nullptr;
     float* ds = ws ? p.dsig + voff(p.vds, q) : nullptr;
     const uintptr_t al = ((uintptr_t)pp) | ((uintptr_t)tp) | ((uintptr_t)sp) | ((uintptr_t)dp) |
@@ -206,7 +266,7 @@ __global__ __launch_bounds__(256) void e2loss_bwd_kernel(LossP p) {
       const loss_f4 pv = *reinterpret_cast<const loss_f4*>(pp);
       const loss_f4 tv = *reinterpret_cast<const loss_f4*>(tp);
       loss_f4 sv = pv;
-      if (KIND == E2_LOSS_GAUSS_NLL) sv = *reinterpret_cast<const loss_f4*>(sp);
+      if (E2I_TWO_PRED(KIND)) sv = *reinterpret_cast<const loss_f4*>(sp);
       float p0, p1, p2, p3, g0, g1, g2, g3;
       bwd_elem<KIND, MARGIN, SC, FLAG>(pv[0], sv[0], tv[0], m, sc, co, p0, g0);
       bwd_elem<KIND, MARGIN, SC, FLAG>(pv[1], sv[1], tv[1], m, sc, co, p1, g1);
@@ -496,6 +556,51 @@ extern "C" int e2_loss_bwd(e2_ctx* ctx, const e2_loss_term* term, const e2_tenso
       else launch_bwd<E2_LOSS_GAUSS_NLL, false, false, false>(ctx, wgs, p, acc);
       break;
   }
+  E2_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- BetaNLL (loss.py:890-950): entry points of its own; the slab rows are e2_loss_fwd's and the
+// term is a GAUSS_NLL-kind row of e2_loss_mix (a plain mean over n_tot, no mask)
+extern "C" int e2_beta_nll_fwd(e2_ctx* ctx, const e2_tensor5* mode, const e2_tensor5* conc,
+                               const e2_tensor5* target, float* partials) {
+  E2_REQUIRE(ctx && mode && conc && target && partials && mode->ptr && conc->ptr && target->ptr,
+             "e2_beta_nll_fwd: null argument");
+  E2_REQUIRE((((uintptr_t)partials) & 15) == 0, "e2_beta_nll_fwd: partials must be 16-byte aligned");
+  E2_REQUIRE(same_size(mode, target) && same_size(mode, conc), "e2_beta_nll_fwd: size mismatch");
+  LossP p = LossP{};
+  const e2_tensor5* v[3] = {mode, target, conc};
+  LView* lv[3] = {&p.vp, &p.vt, &p.vs};
+  if (int rc = loss_geometry(v, 3, p, lv, "e2_beta_nll_fwd")) return rc;
+  p.pred = mode->ptr; p.tgt = target->ptr; p.sig = conc->ptr; p.partials = partials;
+  launch_fwd<E2I_LOSS_BETA_NLL, false, false, false>(ctx, loss_wgs(n_elem(mode), E2_LOSS_FWD_CAP), p);
+  E2_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int e2_beta_nll_bwd(e2_ctx* ctx, const e2_tensor5* mode, const e2_tensor5* conc,
+                               const e2_tensor5* target, const float* coef,
+                               const e2_tensor5* dmode, const e2_tensor5* dconc, int accumulate) {
+  E2_REQUIRE(ctx && mode && conc && target && coef && mode->ptr && conc->ptr && target->ptr,
+             "e2_beta_nll_bwd: null argument");
+  const bool wp = dmode && dmode->ptr, ws = dconc && dconc->ptr;
+  E2_REQUIRE(wp || ws, "e2_beta_nll_bwd: no gradient view given");
+  E2_REQUIRE(same_size(mode, target) && same_size(mode, conc) && (!wp || same_size(mode, dmode)) &&
+                 (!ws || same_size(mode, dconc)), "e2_beta_nll_bwd: size mismatch");
+  LossP p = LossP{};
+  const e2_tensor5* v[5];
+  LView* lv[5];
+  int nv = 0;
+  v[nv] = mode; lv[nv++] = &p.vp;
+  v[nv] = target; lv[nv++] = &p.vt;
+  v[nv] = conc; lv[nv++] = &p.vs;
+  if (wp) { v[nv] = dmode; lv[nv++] = &p.vdp; }
+  if (ws) { v[nv] = dconc; lv[nv++] = &p.vds; }
+  if (int rc = loss_geometry(v, nv, p, lv, "e2_beta_nll_bwd")) return rc;
+  p.pred = mode->ptr; p.tgt = target->ptr; p.sig = conc->ptr;
+  p.dpred = wp ? dmode->ptr : nullptr; p.dsig = ws ? dconc->ptr : nullptr; p.coef = coef;
+  launch_bwd<E2I_LOSS_BETA_NLL, false, false, false>(ctx, loss_wgs(n_elem(mode), E2_LOSS_BWD_CAP), p,
+                                                     accumulate != 0);
   E2_CHECK_HIP(hipGetLastError());
   return 0;
 }

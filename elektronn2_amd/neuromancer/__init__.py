@@ -7,7 +7,8 @@ from .node_basic import (Node, Input, Input_like, split, SplitPart, Concat, Add,
 from .neural import (Conv, UpConv, Pool, Crop, Pad, AutoMerge, UpConvMerge, FragmentsToDense, Perceptron,
                      LRN)
 from .loss import (Softmax, MultinoulliNLL, MalisNLL, SquaredLoss, AbsLoss, BinaryNLL,
-                   GaussianNLL, AggregateLoss, Classification, Errors)
+                   GaussianNLL, BetaNLL, OneHot, EuclideanDistance, RampLoss, AggregateLoss,
+                   Classification, Errors)
 from .optimiser import Optimiser, SGD, AdaGrad, AdaDelta, Adam
 from .model import Model, modelload, params_from_model_file
 from .options import set_plan_options, plan_options

@@ -48,6 +48,24 @@ gradient.  ``margin``, ``scale_correction`` and ``mixing_weights`` are non-train
 kernels read in place.  Mixing these with a MultinoulliNLL / MalisNLL raises NotImplementedError
 (their fused launches take no scale), and so does the ``'s'`` sample axis.
 
+The rest of the reference's loss nodes (loss.py:96-138, 890-950, 1104-1212), terms of the same mix:
+``BetaNLL(mode, concentration, target)``, the negative log density of a Beta distribution, is an
+element-wise loss with entry points of its own (e2_beta_nll_fwd / e2_beta_nll_bwd, csrc/
+loss_elem.hip, with an f32 digamma for the gradient) and a plain mean over all elements, like
+GaussianNLL; ``mode`` and ``concentration`` are used as given (c > 2, 0 < m < 1 is the caller's
+business: a 'sigmoid' head, a 'soft+' head plus an offset).  ``EuclideanDistance(pred, target)``
+(the L2 norm over the feature axis, NaN as 0) and ``RampLoss(d_low, d_big, margin=...)`` (the hinge
+mean_f max(d_low - d_big + margin, 0): over two distances the triplet loss) are ordinary nodes with
+a ONE-feature output the plan materialises (csrc/loss_map.hip); both parents of either may be
+network branches and receive gradients.  As a parent of an ``AggregateLoss`` such a map is one
+more term: the aggregate sums it into a slab (e2_mean_fwd) in front of its mix launch and writes
+coef_k into the map's gradient (e2_mean_bwd) ahead of the map's own backward;
+``term_value`` / ``n_labelled`` (all elements of the map) work as for the others.  Where a distance
+is 0, or was a NaN, its gradient is an exact 0 in every feature (the reference: 0/0).
+``OneHot(target, n_class)`` turns a class-id target into ``n_class`` features of 0 / 1 (exact
+equality, no gradient): the target of a SquaredLoss / BinaryNLL over an n_class-feature
+prediction.  ``BlockedMultinoulliNLL`` is not provided: the reference's computes MultinoulliNLL.
+
 Multi-task nets: ``AggregateLoss`` over 2..8 distinct ``MultinoulliNLL`` terms (sparse targets,
 ``n_indep = 1``, unweighted), each over a ``Softmax`` of its own -- usually K ``(1,1,1)`` 'lin' heads
 on one trunk, the targets cut from one Input by ``node_basic.split`` -- is the form ``multi_nll``:
@@ -70,7 +88,8 @@ from .node_basic import Node, Sym
 from .variables import VariableParam
 
 __all__ = ['Softmax', 'MultinoulliNLL', 'MalisNLL', 'SquaredLoss', 'AbsLoss', 'BinaryNLL',
-           'GaussianNLL', 'AggregateLoss', 'Classification', 'Errors']
+           'GaussianNLL', 'BetaNLL', 'OneHot', 'EuclideanDistance', 'RampLoss', 'AggregateLoss',
+           'Classification', 'Errors']
 
 MAX_LOSS_TERMS = 8     # E2_MAX_LOSS_TERMS of include/e2hip.h
 
@@ -591,11 +610,13 @@ class _ElementLoss(Node):
             return
         if dp is not None and ds is not None and fp != fs:
             # (one of the two buffers already holds another consumer's gradient)
-            plan.ctx.loss_bwd(self._term(plan), pred, sig, target, coef, dp, None, not fp)
-            plan.ctx.loss_bwd(self._term(plan), pred, sig, target, coef, None, ds, not fs)
+            self._launch_bwd(plan, pred, sig, target, coef, dp, None, not fp)
+            self._launch_bwd(plan, pred, sig, target, coef, None, ds, not fs)
             return
-        plan.ctx.loss_bwd(self._term(plan), pred, sig, target, coef, dp, ds,
-                          not (fp if dp is not None else fs))
+        self._launch_bwd(plan, pred, sig, target, coef, dp, ds, not (fp if dp is not None else fs))
+
+    def _launch_bwd(self, plan, pred, sig, target, coef, dp, ds, acc):
+        plan.ctx.loss_bwd(self._term(plan), pred, sig, target, coef, dp, ds, acc)
 
     def _mix_value(self, what):
         plan = self._last_plan
@@ -698,6 +719,196 @@ class GaussianNLL(_ElementLoss):
         return (self.mu, self.sig)
 
 
+class BetaNLL(_ElementLoss):
+    """loss.py:890-950.  The negative log density of a Beta distribution given by its ``mode`` m
+    and ``concentration`` c, at a target x in [0, 1], plus softplus(-c), per element:
+    a = m (c - 2) + 1, b = (1 - m)(c - 2) + 1,
+    -[lgamma(a + b) - lgamma(a) - lgamma(b) + (a - 1) log(x + EPS) + (b - 1) log(1 - x + EPS)].
+    No mask.  ``mode`` and ``concentration`` are used as given (the reference's "exp(.) + 2" remark
+    is stale): feed ``mode`` from a 'sigmoid' node and ``concentration`` from a 'soft+' node plus an
+    offset, so that c > 2 and 0 < m < 1; outside that domain nothing is guarded.  Entry points of
+    its own (e2_beta_nll_fwd / e2_beta_nll_bwd); in the mix it is a plain mean over all elements,
+    as GaussianNLL is."""
+    kind = 'gauss_nll'        # (its row of e2_loss_mix: L = S1 / n_tot)
+
+    def __init__(self, mode, concentration, target, name="beta_nll", print_repr=True):
+        super(BetaNLL, self).__init__((mode, concentration, target), name, print_repr)
+        self.target = target
+        self.mode = mode
+        self.pred = mode
+        self.concentration = concentration
+        self._check_shapes(mode, [('concentration', concentration), ('target', target)])
+
+    def _views(self, plan):
+        return plan.out[self.mode], plan.out[self.concentration], plan.out[self.target]
+
+    def _grad_targets(self):
+        return (self.mode, self.concentration)
+
+    def _plan_fwd(self, plan):
+        mode, conc, target = self._views(plan)
+        plan.ctx.beta_nll_fwd(mode, conc, target, plan.scratch[self, 'partials'])
+
+    def _launch_bwd(self, plan, mode, conc, target, coef, dm, dc, acc):
+        plan.ctx.beta_nll_bwd(mode, conc, target, coef, dm, dc, acc)
+
+
+class OneHot(Node):
+    """loss.py:96-138.  A class-id target (one feature) as ``n_class`` features of 0 / 1: what a
+    SquaredLoss / BinaryNLL over an ``n_class``-feature prediction is held against.  The equality
+    is exact: negative, fractional or NaN ids and ids >= n_class give a column of zeros.  One
+    launch (e2_onehot, csrc/loss_map.hip), no gradient."""
+
+    def __init__(self, target, n_class, axis='f', name="onehot", print_repr=True):
+        super(OneHot, self).__init__(target, name, print_repr)
+        if axis != 'f':
+            raise NotImplementedError("OneHot: the class axis is the feature axis 'f'")
+        if 's' in target.shape.tags:
+            raise NotImplementedError("OneHot: the 's' sample axis is outside the HIP hot path")
+        if target.shape['f'] != 1:
+            raise ValueError("OneHot: the target must have one feature (the class id), got %s"
+                             % (target.shape,))
+        if int(n_class) < 1:
+            raise ValueError("OneHot: n_class = %r" % (n_class,))
+        self.target = target
+        self.axis = target.shape.tag2index('f')
+        self.n_class = int(n_class)
+
+    def _calc_shape(self):
+        self.shape = self.parent.shape.updateshape(self.axis, self.n_class)
+
+    def _plan_alloc(self, plan):
+        if plan.needs_grad(self):
+            raise NotImplementedError("OneHot '%s': trainable parameters upstream of a class-id "
+                                      "target (the node has no gradient)" % (self.name,))
+        if plan.out.get(self.parent) is None:
+            raise NotImplementedError("OneHot: the output of '%s' is not materialised by the plan"
+                                      % (self.parent.name,))
+        plan.alloc_out(self)
+
+    def _plan_fwd(self, plan):
+        plan.ctx.onehot(plan.out[self.parent], plan.out[self])
+
+    def _plan_bwd(self, plan):
+        pass
+
+
+class _MapLoss(Node):
+    """What EuclideanDistance / RampLoss share: an ordinary node whose output -- a ONE-feature map
+    made over the feature axis of two parents of one shape -- the plan materialises, and whose two
+    parents may BOTH need a gradient (csrc/loss_map.hip).  Under an AggregateLoss the term is the
+    mean of the map: the aggregate issues e2_mean_fwd / e2_mean_bwd for it, and ``term_value`` /
+    ``n_labelled`` (all elements of the map: there is no mask) work as for the element-wise
+    losses."""
+
+    def _check_shapes(self, a, b):
+        if 's' in a.shape.tags:
+            raise NotImplementedError("%s: the 's' sample axis is outside the HIP hot path"
+                                      % type(self).__name__)
+        if a is b:
+            # (the value is a constant; both gradient views of one launch would be one buffer)
+            raise ValueError("%s: both parents are the node '%s'" % (type(self).__name__, a.name))
+        if tuple(a.shape.shape) != tuple(b.shape.shape) or \
+                tuple(a.shape.tags) != tuple(b.shape.tags):
+            raise ValueError("%s: both parents must have one shape, got %s and %s"
+                             % (type(self).__name__, a.shape, b.shape))
+        self._last_plan = None
+
+    def _calc_shape(self):
+        self.shape = self.parent[0].shape.updateshape(self.parent[0].shape.tag2index('f'), 1)
+
+    def _calc_comp_cost(self):
+        self.computational_cost = self.parent[0].shape.stripnone_prod
+
+    def _term(self, plan):
+        """the descriptor e2_loss_mix reads for the mean of this map: a plain mean over n_tot
+        elements is the mix's GAUSS_NLL row (include/e2hip.h)"""
+        t = plan.scratch.get((self, 'term'))
+        if t is None:
+            from .. import backend
+            t = plan.scratch[self, 'term'] = backend.loss_term('gauss_nll')
+        return t
+
+    def _plan_alloc(self, plan):
+        for n in self.parent:
+            if plan.out.get(n) is None:
+                raise NotImplementedError("%s: the output of '%s' is not materialised by the plan"
+                                          % (type(self).__name__, n.name))
+        plan.alloc_out(self)
+
+    def _slots(self, plan):
+        """((buffer or None, accumulate), ...) of the two parents' output gradients"""
+        r = []
+        for n in self.parent:
+            if plan.needs_grad(n):
+                dst, first = plan.grad_slot(n)
+                r.append((dst, not first))
+            else:
+                r.append((None, False))
+        return r
+
+    _mix_value = _ElementLoss._mix_value
+    term_value = _ElementLoss.term_value
+
+    @property
+    def n_labelled(self):
+        """all elements of the map (there is no mask): the host's n_tot of the plan that ran last,
+        not the slab's float count, which is exact only below 2^24 elements"""
+        if self._mix_value('count') is None:
+            return None
+        return self._last_plan.scratch[self, 'n_tot']
+
+
+class EuclideanDistance(_MapLoss):
+    """loss.py:1104-1151.  sqrt(sum_f (target - pred)^2) per position, one feature; a NaN result
+    is 0.  ``pred`` and ``target`` may both be network branches.  Where the distance is 0 (or was
+    a NaN) every feature's gradient is an exact 0 (the reference: 0/0)."""
+
+    def __init__(self, pred, target, name="se", print_repr=True):
+        super(EuclideanDistance, self).__init__((pred, target), name, print_repr)
+        self.target = target
+        self.pred = pred
+        self._check_shapes(pred, target)
+
+    def _plan_fwd(self, plan):
+        plan.ctx.fdist_fwd(plan.out[self.pred], plan.out[self.target], plan.out[self])
+
+    def _plan_bwd(self, plan):
+        (dp, ap), (dt, at) = self._slots(plan)
+        if dp is None and dt is None:
+            return
+        plan.ctx.fdist_bwd(plan.out[self.pred], plan.out[self.target], plan.out[self],
+                           plan.grad[self], dp, dt, ap, at)
+
+
+class RampLoss(_MapLoss):
+    """loss.py:1154-1212.  mean_f max(d_low - d_big + margin, 0) per position (NaN as 0), one
+    feature: over two EuclideanDistance nodes the triplet loss.  ``margin`` is a non-trainable
+    parameter (0 when None) the kernels read in place.  The slope at exactly 0 is 1."""
+
+    def __init__(self, d_low, d_big, name="se", print_repr=True, margin=None):
+        super(RampLoss, self).__init__((d_low, d_big), name, print_repr)
+        if margin is None:
+            margin = 0
+        margin = VariableParam(value=margin, name="margin", dtype=floatX, apply_train=False)
+        self.params['margin'] = margin
+        self.margin = margin
+        self.d_low = d_low
+        self.d_big = d_big
+        self._check_shapes(d_low, d_big)
+
+    def _plan_fwd(self, plan):
+        plan.ctx.ramp_fwd(plan.out[self.d_low], plan.out[self.d_big],
+                          plan.param(self.margin).reshape(-1), plan.out[self])
+
+    def _plan_bwd(self, plan):
+        (dl, al), (db, ab) = self._slots(plan)
+        if dl is None and db is None:
+            return
+        plan.ctx.ramp_bwd(plan.out[self.d_low], plan.out[self.d_big],
+                          plan.param(self.margin).reshape(-1), plan.grad[self], dl, db, al, ab)
+
+
 class AggregateLoss(Node):
     def __init__(self, parent_nodes, mixing_weights=None, name="total_loss", print_repr=True):
         if not isinstance(parent_nodes, (tuple, list)):
@@ -717,11 +928,12 @@ class AggregateLoss(Node):
         self.params['mixing_weights'] = mixing_weights
         self.mixing_weights = mixing_weights
         # three forms: exactly one MultinoulliNLL / MalisNLL (their own launches make the loss),
-        # 1..MAX_LOSS_TERMS element-wise losses mixed by this node's launch (csrc/loss_elem.hip),
+        # 1..MAX_LOSS_TERMS element-wise losses mixed by this node's launch (csrc/loss_elem.hip;
+        # a loss MAP -- EuclideanDistance, RampLoss -- counts as one: the term is the map's mean),
         # or 'multi_nll': 2..MAX_LOSS_TERMS distinct plain MultinoulliNLL terms, each over a
         # softmax of its own, run and mixed by this node's launches (csrc/softmax_nll.hip)
         self.elementwise = len(parent_nodes) > 0 and \
-            all(isinstance(n, _ElementLoss) for n in parent_nodes)
+            all(isinstance(n, (_ElementLoss, _MapLoss)) for n in parent_nodes)
         self.multi_nll = (
             2 <= len(parent_nodes) <= MAX_LOSS_TERMS
             and all(isinstance(n, MultinoulliNLL) and n.n_indep == 1 and not n.weighted
@@ -790,6 +1002,10 @@ class AggregateLoss(Node):
             for k, n in enumerate(self.parent):
                 plan.scratch[n, 'agg'] = (self, k)
                 n._last_plan = plan
+                if isinstance(n, _MapLoss):       # (the mean of the map is this node's launch)
+                    m = plan.out[n]
+                    plan.scratch[n, 'partials'] = plan.empty_flat(4 * plan.ctx.loss_partials(m))
+                    plan.scratch[n, 'n_tot'] = int(m.numel())
             for what in ('coef', 'term_loss', 'count'):
                 plan.scratch[self, what] = plan.zeros_flat(MAX_LOSS_TERMS)
             plan.scratch[self, 'loss'] = plan.zeros_flat(1)
@@ -825,6 +1041,9 @@ class AggregateLoss(Node):
         if not self.elementwise:           # (multi_nll: _emit_fwd, issued by the last Softmax)
             return
         ps = list(self.parent)
+        for n in ps:
+            if isinstance(n, _MapLoss):
+                plan.ctx.mean_fwd(plan.out[n], plan.scratch[n, 'partials'])
         plan.ctx.loss_mix([n._term(plan) for n in ps], [plan.scratch[n, 'partials'] for n in ps],
                           [plan.scratch[n, 'n_tot'] for n in ps],
                           plan.param(self.mixing_weights).reshape(-1), plan.scratch[self, 'coef'],
@@ -861,8 +1080,14 @@ class AggregateLoss(Node):
                                    [plan.out[n.target] for n in ps],
                                    plan.scratch[self, 'coef'], dsts)
             return
-        pass          # d(total)/d(nll) = mixing_weight(=1) / 1 ; folded into the NLL backward
-                      # (element-wise losses: coef[k], which each term's backward launch reads)
+        # d(total)/d(nll) = mixing_weight(=1) / 1 ; folded into the NLL backward
+        # (element-wise losses: coef[k], which each term's backward launch reads; a loss map's
+        # own backward runs behind this node's: its output gradient is coef[k] everywhere)
+        if self.elementwise:
+            for k, n in enumerate(self.parent):
+                if isinstance(n, _MapLoss) and plan.needs_grad(n):
+                    dst, first = plan.grad_slot(n)
+                    plan.ctx.mean_bwd(plan.scratch[self, 'coef'][k:k + 1], dst, not first)
 
     def loss_dev(self, plan):
         """the one-element device tensor that holds the step's loss"""

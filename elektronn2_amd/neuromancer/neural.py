@@ -171,6 +171,8 @@ class NeuralLayer(Node):
                                  % (shape, param.get_value().shape))
             p = param
             add_to_params = False
+            # (not in `params`, which names the owner alone: Plan.needs_grad reads this list)
+            self.__dict__.setdefault('borrowed_params', []).append(p)
         elif isinstance(param, (list, tuple)):
             if not isinstance(param[0], np.ndarray) or param[1] not in ('const', 'trainable'):
                 raise ValueError("If a parameter is passed as a list, the first entry "

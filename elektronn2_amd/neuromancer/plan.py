@@ -245,12 +245,16 @@ class Plan(object):
 
     def needs_grad(self, node):
         """gradient wrt this node's output is required: it is on the loss path
-        and some trainable parameter lies upstream of (or in) it."""
+        and some trainable parameter lies upstream of (or in) it -- its own, or one it borrows
+        from another node (``w=<other>.w``: the branches of a siamese net own nothing, and their
+        contributions to the shared gradient slots are still due)."""
         if not self.training or id(node) not in self._loss_anc:
             return False
         r = self._ng_cache.get(id(node))
         if r is None:
-            r = len(node.all_trainable_params) > 0
+            r = len(node.all_trainable_params) > 0 or any(
+                p.apply_train for a in node.all_parents.values()
+                for p in getattr(a, 'borrowed_params', ()))
             self._ng_cache[id(node)] = r
         return r
 

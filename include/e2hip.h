@@ -1126,6 +1126,69 @@ int e2_loss_bwd(e2_ctx*, const e2_loss_term*, const e2_tensor5* pred, const e2_t
                 const e2_tensor5* target, const float* coef, const e2_tensor5* dpred,
                 const e2_tensor5* dsig, int accumulate);
 
+/* ---- losses over the feature axis and the mean of a loss map (csrc/loss_map.hip; loss.py:
+ *      1104-1151 EuclideanDistance, 1154-1212 RampLoss, 1346-1363 AggregateLoss) -----------------
+ * All operands are strided views of the same n, d, h, w; the maps have ONE feature.
+ *
+ *   op      forward (a map, one feature)                        backward (dm: the map's gradient)
+ *   fdist   m = sqrt(sum_f (t - p)^2), a NaN m is stored as 0   dp = -(t - p) / m * dm,  dt = -dp
+ *   ramp    m = (1/F) sum_f r,  r = d_low - d_big + margin,     dd_low = dm / F where r >= 0 and r is
+ *           r < 0 -> 0, then NaN -> 0                           not NaN, else 0;  dd_big = -dd_low
+ *   mean    rows (sum x, elements summed, 0, 0)                 dx = coef[0] in every element
+ *
+ * The reference masks r < 0 only: the slope of the ramp AT r == 0 is 1.
+ * Two departures from the reference's gradient of fdist: where m == 0 (p == t over all features)
+ * T.grad gives 0/0 = NaN, here EVERY feature receives an exact 0; where the forward replaced a NaN
+ * by 0, likewise an exact 0 in every feature.
+ * The mean of a map is a term of e2_loss_mix, which is unchanged by it: e2_mean_fwd writes the slab
+ * rows of e2_loss_fwd -- (S1, n, S2, 0) per work-group, plain 16-byte stores, no atomics,
+ * e2_loss_partials(x) rows -- and the term is normalised by n_tot (a plain mean, no -666 mask),
+ * which is the GAUSS_NLL row of the mix: L = S1 / n_tot, coef = mix / (K n_tot).  The caller hands
+ * e2_loss_mix a GAUSS_NLL-kind descriptor for such a term.
+ * margin and coef are DEVICE scalars read when the kernels run.  A gradient view may be NULL (not
+ * wanted), not both; each has its own accumulate flag (!= 0 adds to what the view holds): in a
+ * siamese net both parents are network branches and either may hold another consumer's gradient.
+ * Nothing outside a view is read or written.  All arithmetic is f32. */
+int e2_fdist_fwd(e2_ctx*, const e2_tensor5* pred, const e2_tensor5* target, const e2_tensor5* out);
+int e2_fdist_bwd(e2_ctx*, const e2_tensor5* pred, const e2_tensor5* target, const e2_tensor5* out,
+                 const e2_tensor5* dout, const e2_tensor5* dpred, const e2_tensor5* dtarget,
+                 int acc_pred, int acc_target);
+int e2_ramp_fwd(e2_ctx*, const e2_tensor5* d_low, const e2_tensor5* d_big, const float* margin,
+                const e2_tensor5* out);
+int e2_ramp_bwd(e2_ctx*, const e2_tensor5* d_low, const e2_tensor5* d_big, const float* margin,
+                const e2_tensor5* dout, const e2_tensor5* dd_low, const e2_tensor5* dd_big,
+                int acc_low, int acc_big);
+/* partials: e2_loss_partials(x) rows of 4 floats, 16-byte aligned, every row written.  The second
+ * column (elements summed, which the mix reports as count) is informational: the GAUSS_NLL row
+ * normalises by the host's n_tot, and as a float sum the column is exact only below 2^24 elements
+ * per row's work-group and 2^53 in the mix's double sum of rows. */
+int e2_mean_fwd(e2_ctx*, const e2_tensor5* x, float* partials);
+int e2_mean_bwd(e2_ctx*, const float* coef, const e2_tensor5* dx, int accumulate);
+/* OneHot (loss.py:96-138): out[n,k,z,y,x] = (target[n,0,z,y,x] == k) ? 1 : 0 as float for k <
+ * n_class = the features of out.  The equality is exact: a negative, fractional or NaN id, or
+ * one >= n_class, gives a column of zeros.  No gradient. */
+int e2_onehot(e2_ctx*, const e2_tensor5* target, int n_class, const e2_tensor5* out);
+
+/* ---- BetaNLL (csrc/loss_elem.hip; loss.py:890-950) ---------------------------------------------
+ * m mode, c concentration, x target in [0, 1], all of one size; EPS = 1e-5;
+ * a = m (c - 2) + 1, b = (1 - m)(c - 2) + 1:
+ *   l = -[lgamma(a + b) - lgamma(a) - lgamma(b) + (a - 1) log(x + EPS) + (b - 1) log(1 - x + EPS)]
+ *       + softplus(-c),                     no mask,   L = S1 / n_tot
+ *   dl/dm = (c - 2) [psi(a) - psi(b) - log(x + EPS) + log(1 - x + EPS)]
+ *   dl/dc = -psi(a + b) + m psi(a) + (1 - m) psi(b) - m log(x + EPS) - (1 - m) log(1 - x + EPS)
+ *           - sigmoid(-c)
+ * psi (digamma) is an f32 device function of the library: the recurrence up to an argument >= 6,
+ * then the asymptotic series.  Domain: c > 2 and 0 < m < 1, so a, b > 1; outside it the kernels
+ * follow the formula as far as lgammaf does and guard nothing.
+ * The forward writes the slab rows of e2_loss_fwd (e2_loss_partials(mode) rows); the term goes
+ * into e2_loss_mix under a GAUSS_NLL-kind descriptor (the same plain mean over n_tot), and the
+ * backward reads the coef the mix wrote.  dmode or dconc may be NULL, not both. */
+int e2_beta_nll_fwd(e2_ctx*, const e2_tensor5* mode, const e2_tensor5* conc,
+                    const e2_tensor5* target, float* partials);
+int e2_beta_nll_bwd(e2_ctx*, const e2_tensor5* mode, const e2_tensor5* conc,
+                    const e2_tensor5* target, const float* coef, const e2_tensor5* dmode,
+                    const e2_tensor5* dconc, int accumulate);
+
 #ifdef __cplusplus
 }
 #endif
