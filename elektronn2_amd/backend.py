@@ -259,6 +259,9 @@ def _load():
         "e2_onehot": (C.c_int, [vp, P5, i, P5]),
         "e2_beta_nll_fwd": (C.c_int, [vp, P5, P5, P5, fp]),
         "e2_beta_nll_bwd": (C.c_int, [vp, P5, P5, P5, fp, P5, P5, i]),
+        "e2_sobel_abs_partials": (sz, [vp, P5]),
+        "e2_sobel_abs_fwd": (C.c_int, [vp, PL, i, P5, P5, fp]),
+        "e2_sobel_abs_bwd": (C.c_int, [vp, PL, i, P5, P5, fp, P5, i]),
         "e2_adam_step": (C.c_int, [vp, fp, fp, fp, fp, sz, vp, fp, i, fp]),
         "e2_sgd_step": (C.c_int, [vp, fp, fp, fp, sz, vp, fp, i, fp]),
         "e2_set_loss_grad_mode": (C.c_int, [vp, i, fp]),
@@ -820,6 +823,29 @@ class Context:
         _chk(_lib.e2_beta_nll_bwd(self.h, C.byref(t5(mode)), C.byref(t5(conc)),
                                   C.byref(t5(target)), _fp(coef), opt(dmode), opt(dconc),
                                   int(bool(accumulate))), "e2_beta_nll_bwd")
+
+    # ---- SobelizedLoss: separable Sobel filters + AbsLoss (csrc/loss_sobel.hip) ------------------
+    def sobel_partials(self, pred):
+        """rows of 4 floats that sobel_abs_fwd writes for this prediction"""
+        n = int(_lib.e2_sobel_abs_partials(self.h, C.byref(t5(pred))))
+        if n <= 0:
+            raise E2Error("e2_sobel_abs_partials: empty prediction %s" % (tuple(pred.shape),))
+        return n
+
+    def sobel_abs_fwd(self, term, dim, pred, target, partials):
+        """slab rows (S1, n_lab, S2, 0) of |S_k target - S_k pred| over the ``dim`` Sobel components:
+        a term of loss_mix under ``term`` (kind 'abs') with n_tot = dim * pred.numel()"""
+        if partials.numel() < 4 * self.sobel_partials(pred):
+            raise E2Error("sobel_abs_fwd: the partials slab is too small for this prediction")
+        _chk(_lib.e2_sobel_abs_fwd(self.h, C.byref(term), int(dim), C.byref(t5(pred)),
+                                   C.byref(t5(target)), _fp(partials)), "e2_sobel_abs_fwd")
+
+    def sobel_abs_bwd(self, term, dim, pred, target, coef, dpred, accumulate=False):
+        """dpred (=|+=) coef * d(term sum)/d(pred); ``coef``: the one-element device tensor loss_mix
+        wrote for the term"""
+        _chk(_lib.e2_sobel_abs_bwd(self.h, C.byref(term), int(dim), C.byref(t5(pred)),
+                                   C.byref(t5(target)), _fp(coef), C.byref(t5(dpred)),
+                                   int(bool(accumulate))), "e2_sobel_abs_bwd")
 
     def mean_bwd(self, coef, dx, accumulate=False):
         """dx (=|+=) coef[0]; ``coef``: the one-element device tensor loss_mix wrote"""

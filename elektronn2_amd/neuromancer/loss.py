@@ -1,6 +1,6 @@
-"""Softmax / MultinoulliNLL / SquaredLoss / AbsLoss / BinaryNLL / GaussianNLL / AggregateLoss /
-Errors with the reference's constructor signatures (elektronn2/neuromancer/loss.py:33-93,
-141-351, 693-826, 829-887, 953-1101, 1215-1370).
+"""Softmax / MultinoulliNLL / SquaredLoss / AbsLoss / BinaryNLL / GaussianNLL / SobelizedLoss /
+AggregateLoss / Errors with the reference's constructor signatures (elektronn2/neuromancer/
+loss.py:33-93, 141-351, 693-826, 829-887, 953-1101, 1215-1439).
 
 HIP execution covers the pattern every BASELINE config uses:
 ``AggregateLoss(MultinoulliNLL(Softmax(lin-Conv), target, target_is_sparse=True))``
@@ -66,6 +66,14 @@ is 0, or was a NaN, its gradient is an exact 0 in every feature (the reference: 
 equality, no gradient): the target of a SquaredLoss / BinaryNLL over an n_class-feature
 prediction.  ``BlockedMultinoulliNLL`` is not provided: the reference's computes MultinoulliNLL.
 
+``SobelizedLoss(pred, target, loss_kwargs=dict(margin=...))`` (loss.py:1373-1439) is an AbsLoss
+between the Sobel-filtered prediction and the Sobel-filtered target -- per feature one derivative
+filter [1, 0, -1] per spatial axis, smoothed by [0.3, 0.4, 0.3] along the other axes, over the
+zero-framed map -- and one more element-wise term of the mix with ``dim`` times the prediction's
+elements.  It is ONE node and one stencil launch each way (csrc/loss_sobel.hip, the formulas in
+include/e2hip.h): the reference's ``pred_sobel`` / ``target_sobel`` Conv nodes with constant
+weights do not exist, the filtered tensors are never written.  No gradient goes to the target.
+
 Multi-task nets: ``AggregateLoss`` over 2..8 distinct ``MultinoulliNLL`` terms (sparse targets,
 ``n_indep = 1``, unweighted), each over a ``Softmax`` of its own -- usually K ``(1,1,1)`` 'lin' heads
 on one trunk, the targets cut from one Input by ``node_basic.split`` -- is the form ``multi_nll``:
@@ -88,8 +96,8 @@ from .node_basic import Node, Sym
 from .variables import VariableParam
 
 __all__ = ['Softmax', 'MultinoulliNLL', 'MalisNLL', 'SquaredLoss', 'AbsLoss', 'BinaryNLL',
-           'GaussianNLL', 'BetaNLL', 'OneHot', 'EuclideanDistance', 'RampLoss', 'AggregateLoss',
-           'Classification', 'Errors']
+           'GaussianNLL', 'BetaNLL', 'OneHot', 'EuclideanDistance', 'RampLoss', 'SobelizedLoss',
+           'AggregateLoss', 'Classification', 'Errors']
 
 MAX_LOSS_TERMS = 8     # E2_MAX_LOSS_TERMS of include/e2hip.h
 
@@ -751,6 +759,65 @@ class BetaNLL(_ElementLoss):
 
     def _launch_bwd(self, plan, mode, conc, target, coef, dm, dc, acc):
         plan.ctx.beta_nll_bwd(mode, conc, target, coef, dm, dc, acc)
+
+
+class SobelAbsLoss(AbsLoss):
+    """The node ``SobelizedLoss`` returns: AbsLoss(S pred, S target), where S gives ``dim``
+    features per feature of its argument -- component k the filter [1, 0, -1] along spatial axis k
+    times [0.3, 0.4, 0.3] along the others, zero-framed ('same').  The mask and
+    ``scale_correction`` look at the FILTERED target, as in the reference; ``n_labelled`` counts
+    ``dim`` elements per element of ``pred``.  Both operands are filtered inside the node's own two
+    launches (e2_sobel_abs_fwd / e2_sobel_abs_bwd, csrc/loss_sobel.hip); the filtered tensors never
+    exist in memory.  The target receives no gradient: trainable parameters upstream of it raise
+    when the plan is made."""
+
+    def __init__(self, pred, target, margin=None, scale_correction=None, name="absloss",
+                 print_repr=True):
+        super(SobelAbsLoss, self).__init__(pred, target, margin=margin,
+                                           scale_correction=scale_correction, name=name,
+                                           print_repr=print_repr)
+        tags = tuple(pred.shape.tags)
+        if tags == ('b', 'f', 'z', 'x', 'y'):
+            self.dim = 3
+        elif tags in (('b', 'f', 'x', 'y'), ('b', 'f', 'y', 'x')):
+            self.dim = 2
+        else:
+            raise NotImplementedError("SobelizedLoss: a prediction with axes %s; 'b,f,z,x,y', "
+                                      "'b,f,x,y' and 'b,f,y,x' are supported" % ",".join(tags))
+
+    def _plan_alloc(self, plan):
+        if plan.needs_grad(self.target):
+            raise NotImplementedError("SobelizedLoss '%s': trainable parameters upstream of the "
+                                      "target '%s' (the node has no gradient wrt its target)"
+                                      % (self.name, self.target.name))
+        for n in self.parent:
+            if plan.out.get(n) is None:
+                raise NotImplementedError("SobelizedLoss: the output of '%s' is not materialised "
+                                          "by the plan" % (n.name,))
+        pred = plan.out[self.pred]
+        plan.scratch[self, 'partials'] = plan.empty_flat(4 * plan.ctx.sobel_partials(pred))
+        plan.scratch[self, 'n_tot'] = self.dim * int(pred.numel())
+        plan.out[self] = None        # neither the filtered tensors nor the element-wise array exist
+
+    def _plan_fwd(self, plan):
+        pred, _, target = self._views(plan)
+        plan.ctx.sobel_abs_fwd(self._term(plan), self.dim, pred, target,
+                               plan.scratch[self, 'partials'])
+
+    def _launch_bwd(self, plan, pred, sig, target, coef, dp, ds, acc):
+        plan.ctx.sobel_abs_bwd(self._term(plan), self.dim, pred, target, coef, dp, acc)
+
+
+def SobelizedLoss(pred, target, loss_type='abs', loss_kwargs=None):
+    """loss.py:1373-1439.  An AbsLoss between the Sobel-filtered prediction and the Sobel-filtered
+    target; ``loss_kwargs`` are AbsLoss's (``margin``, ``scale_correction``, ``name``,
+    ``print_repr``); only ``loss_type='abs'`` exists, as in the reference.  ``pred`` is
+    ``'b,f,z,x,y'`` or, for two components, ``'b,f,x,y'`` / ``'b,f,y,x'``.  One departure from the
+    reference: it returns ONE node (``SobelAbsLoss``) and puts no ``pred_sobel`` / ``target_sobel``
+    Conv nodes with constant weights into the graph."""
+    if loss_type != 'abs':
+        raise NotImplementedError("SobelizedLoss: loss_type %r (only 'abs')" % (loss_type,))
+    return SobelAbsLoss(pred, target, **(loss_kwargs or {}))
 
 
 class OneHot(Node):

@@ -1169,6 +1169,38 @@ int e2_mean_bwd(e2_ctx*, const float* coef, const e2_tensor5* dx, int accumulate
  * one >= n_class, gives a column of zeros.  No gradient. */
 int e2_onehot(e2_ctx*, const e2_tensor5* target, int n_class, const e2_tensor5* out);
 
+/* ---- SobelizedLoss: separable Sobel filters + AbsLoss in one launch each way (csrc/loss_sobel.hip;
+ *      loss.py:1373-1439) -------------------------------------------------------------------------
+ * p prediction, t target, both (N, F, D, H, W), any strides; dim = 3, or 2 with a unit D (no z
+ * factor, no z component).  For a component k < dim, S_k is the filter [1, 0, -1] along axis k
+ * (out(x) = v(x - 1) - v(x + 1)) times [0.3, 0.4, 0.3] along each other spatial axis, applied to
+ * the ZERO-FRAMED feature map (the reference's two constant-weight 'same' Convs, zero bias):
+ *
+ *   ps = S_k p,  ts = S_k t,  d = ts - ps          n_tot = dim N F D H W such elements
+ *   l  = |d| g c, g = [|d| >= margin], c = sc |ts| + 1: the ABS row of the table above with (ps, ts)
+ *        in the place of (p, t); an element is masked where ts passes the -666 test
+ *   slab rows (S1, n_lab, S2, 0) as e2_loss_fwd's; e2_loss_mix, unchanged, takes an ABS-kind
+ *   descriptor and n_tot and gives L and coef
+ *   dp = -coef sum_k S_k^T s_k,   s_k = sgn(d) g c  (sgn 0 = 0; 0 where masked)
+ *
+ * ZERO OUTSIDE: s_k is defined at the positions inside the tensor only and is zero outside it.
+ * The zero frame gives non-zero ps / ts one position outside the tensor; an s computed from those
+ * never reaches dp.  S_k^T is S_k with the derivative taps negated, i.e. -S_k.
+ * pred_sobel / target_sobel are never written to memory.  No gradient goes to the target.  The
+ * term must be of kind ABS; only margin and scale_correction are read from it, and they and coef
+ * are DEVICE scalars read when the kernels run.  Nothing outside a view is read or written.  All
+ * arithmetic is f32; no atomics: the slab and the loss are bit-reproducible. */
+/* rows of 4 floats e2_sobel_abs_fwd writes for a prediction of these sizes (one per work-group, at
+ * most 1024; the sizes alone decide, dim does not).  0: empty / null view */
+size_t e2_sobel_abs_partials(e2_ctx*, const e2_tensor5* pred);
+/* partials: that many rows, 16-byte aligned, every row written by a plain store */
+int e2_sobel_abs_fwd(e2_ctx*, const e2_loss_term*, int dim, const e2_tensor5* pred,
+                     const e2_tensor5* target, float* partials);
+/* dpred (=|+=) the dp above; accumulate != 0 adds to what the view holds */
+int e2_sobel_abs_bwd(e2_ctx*, const e2_loss_term*, int dim, const e2_tensor5* pred,
+                     const e2_tensor5* target, const float* coef, const e2_tensor5* dpred,
+                     int accumulate);
+
 /* ---- BetaNLL (csrc/loss_elem.hip; loss.py:890-950) ---------------------------------------------
  * m mode, c concentration, x target in [0, 1], all of one size; EPS = 1e-5;
  * a = m (c - 2) + 1, b = (1 - m)(c - 2) + 1:
