@@ -259,6 +259,10 @@ def _load():
         "e2_onehot": (C.c_int, [vp, P5, i, P5]),
         "e2_beta_nll_fwd": (C.c_int, [vp, P5, P5, P5, fp]),
         "e2_beta_nll_bwd": (C.c_int, [vp, P5, P5, P5, fp, P5, P5, i]),
+        "e2_gaussrv_fwd": (C.c_int, [vp, P5, P5, P5, vp, C.c_uint32]),
+        "e2_gaussrv_bwd": (C.c_int, [vp, P5, P5, P5, P5, i, i, vp, C.c_uint32]),
+        "e2_aevb_prior_fwd": (C.c_int, [vp, P5, P5, fp]),
+        "e2_aevb_prior_bwd": (C.c_int, [vp, P5, P5, fp, P5, P5, i, i]),
         "e2_sobel_abs_partials": (sz, [vp, P5]),
         "e2_sobel_abs_fwd": (C.c_int, [vp, PL, i, P5, P5, fp]),
         "e2_sobel_abs_bwd": (C.c_int, [vp, PL, i, P5, P5, fp, P5, i]),
@@ -1003,6 +1007,39 @@ class Context:
     def dropout_tick(self, state):
         """state's counter += 1: the launch in front of a step's dropout launches"""
         _chk(_lib.e2_dropout_tick(self.h, self._drop_state(state)), "e2_dropout_tick")
+
+    # ---- GaussianRV and its AEVB prior (csrc/gauss_rv.hip; e2hip.h: the noise contract) ----------
+    def gaussrv_fwd(self, mu, log_sig, out, state, stream):
+        """out = mu + exp(log_sig) * eps; ``state``: the int32[4] device tensor of the dropout
+        launches, read when the kernel RUNS (None reaches the library as NULL and is refused)"""
+        st = None if state is None else self._drop_state(state)
+        _chk(_lib.e2_gaussrv_fwd(self.h, C.byref(t5(mu)), C.byref(t5(log_sig)), C.byref(t5(out)),
+                                 st, int(stream) & 0xffffffff), "e2_gaussrv_fwd")
+
+    def gaussrv_bwd(self, dout, log_sig, dmu, dlog_sig, state, stream, acc_mu=False, acc_sig=False):
+        """dmu (=|+=) dout, dlog_sig (=|+=) dout * eps * exp(log_sig) with the eps of gaussrv_fwd
+        for the same state and stream; either gradient may be None"""
+        opt = lambda t: None if t is None else C.byref(t5(t))
+        st = None if state is None else self._drop_state(state)
+        _chk(_lib.e2_gaussrv_bwd(self.h, C.byref(t5(dout)), C.byref(t5(log_sig)), opt(dmu),
+                                 opt(dlog_sig), int(bool(acc_mu)), int(bool(acc_sig)), st,
+                                 int(stream) & 0xffffffff), "e2_gaussrv_bwd")
+
+    def aevb_prior_fwd(self, mu, log_sig, partials):
+        """slab rows (sum of 0.5 (mu^2 + exp(2 log_sig) - 1 - 2 log_sig), elements, 0, 0): a term
+        of loss_mix under a 'gauss_nll' descriptor"""
+        if partials.numel() < 4 * self.loss_partials(mu):
+            raise E2Error("aevb_prior_fwd: the partials slab is too small for this tensor")
+        _chk(_lib.e2_aevb_prior_fwd(self.h, C.byref(t5(mu)), C.byref(t5(log_sig)), _fp(partials)),
+             "e2_aevb_prior_fwd")
+
+    def aevb_prior_bwd(self, mu, log_sig, coef, dmu, dlog_sig, acc_mu=False, acc_sig=False):
+        """dmu (=|+=) coef[0] * mu, dlog_sig (=|+=) coef[0] * (exp(2 log_sig) - 1); ``coef``: the
+        one-element device tensor loss_mix wrote; either gradient may be None"""
+        opt = lambda t: None if t is None else C.byref(t5(t))
+        _chk(_lib.e2_aevb_prior_bwd(self.h, C.byref(t5(mu)), C.byref(t5(log_sig)), _fp(coef),
+                                    opt(dmu), opt(dlog_sig), int(bool(acc_mu)), int(bool(acc_sig))),
+             "e2_aevb_prior_bwd")
 
     # ---- loss / optimiser ----------------------------------------------------------
     def softmax_nll_fwd(self, logits, target, probs, stats, weights=None):

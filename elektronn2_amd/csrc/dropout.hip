@@ -10,6 +10,7 @@
 // A pure stream: no LDS, no atomics, no cross-work-group traffic; the counter is advanced by a
 // launch of its own (dropout_tick_kernel) in front of the step's dropout launches.
 #include "stream_common.hpp"
+#include "philox.hpp"
 
 namespace {
 
@@ -27,22 +28,6 @@ struct DropP {
   int unit;                     // innermost stride is 1 in both views (16-byte path possible)
 };
 
-struct U4 {
-  unsigned x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
-                                            unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return U4{c0, c1, c2, c3};
-}
 // (a select chain: indexing a register array with a run-time index would go through scratch)
 __device__ __forceinline__ unsigned pick(const U4& r, unsigned i) {
   return i == 0 ? r.x : (i == 1 ? r.y : (i == 2 ? r.z : r.w));

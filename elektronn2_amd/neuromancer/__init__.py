@@ -9,6 +9,7 @@ from .neural import (Conv, UpConv, Pool, Crop, Pad, AutoMerge, UpConvMerge, Frag
 from .loss import (Softmax, MultinoulliNLL, MalisNLL, SquaredLoss, AbsLoss, BinaryNLL,
                    GaussianNLL, BetaNLL, OneHot, EuclideanDistance, RampLoss, SobelizedLoss,
                    AggregateLoss, Classification, Errors)
+from .various import GaussianRV, GaussianAEVBPrior
 from .optimiser import Optimiser, SGD, AdaGrad, AdaDelta, Adam
 from .model import Model, modelload, params_from_model_file
 from .options import set_plan_options, plan_options

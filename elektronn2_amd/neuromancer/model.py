@@ -330,6 +330,11 @@ class Model(GraphManager):
         rate 0 has none, neural.py:246-249)"""
         return [n for n in self.nodes.values() if n.params.get('dropout_rate', None) is not None]
 
+    def gaussian_rv_nodes(self):
+        """the ``GaussianRV`` nodes in node order: they draw from the generator state below (its
+        seed, its one tick per step) on streams numbered behind the dropout nodes'"""
+        return [n for n in self.nodes.values() if type(n).__name__ == 'GaussianRV']
+
     @property
     def dropout_rates(self):
         """model.py:365-376: the rates of the dropout nodes in node order (empty for a net
@@ -359,7 +364,8 @@ class Model(GraphManager):
         -- they share the state) draws the gates of ``(seed, counter)``, the one after it of
         ``counter + 1``, ...  (include/e2hip.h, the gate contract).  Without a call the seed is
         ``int(time.time())``, as the reference seeds its stream.  Neither seed nor
-        counter is part of a checkpoint (the reference reseeds on every build); the rates are."""
+        counter is part of a checkpoint (the reference reseeds on every build); the rates are.
+        The noise of the model's ``GaussianRV`` nodes comes from the same state (various.py:67)."""
         self._drop_host = (int(seed) & 0xffffffffffffffff, int(counter) & 0xffffffff)
         if self._drop_dev is not None:
             self._drop_upload()
@@ -725,7 +731,7 @@ def modelload(file_name, model=None, override_mfp_to_active=False, imposed_patch
     if model is not None:
         model.load(file_name)
         return model
-    from . import node_basic, neural, loss as loss_mod
+    from . import node_basic, neural, loss as loss_mod, various
     z = np.load(file_name, allow_pickle=False)
     if "meta/graph" not in z.files:
         raise ValueError("%s holds parameters only (no graph description): pass the "
@@ -820,7 +826,7 @@ def modelload(file_name, model=None, override_mfp_to_active=False, imposed_patch
 
     new = node_basic.model_manager.newmodel(name)
     classes = {}
-    for mod in (node_basic, neural, loss_mod):
+    for mod in (node_basic, neural, loss_mod, various):
         for k in dir(mod):
             v = getattr(mod, k, None)
             if isinstance(v, type) and issubclass(v, node_basic.Node):

@@ -599,13 +599,36 @@ class SplitPart(Node):
     def _calc_comp_cost(self):
         self.computational_cost = 0
 
+    def _grad_view_ok(self, plan):
+        """a part on the loss path can take its channel slice of the parent's output gradient as
+        its own gradient where every writer handles a strided view with an accumulate flag of its
+        own -- the GaussianRV pair (various.py: mu / log_sig cut from one 2F-feature node) -- and
+        the parts jointly write the whole of the parent's gradient: the parent has no other
+        consumer on the loss path, and every part of it is one of these"""
+        on_path = lambda c: any(n is c for n in plan.nodes) and \
+            (id(c) in plan._loss_anc or c is plan.loss_node)
+        kids = [c for c in self.children.values() if on_path(c)]
+        sibs = [c for c in self.parent.children.values() if on_path(c)]
+        if not kids or not all(getattr(c, '_writes_part_grad', False) for c in kids) \
+                or not all(type(c) is SplitPart and plan.needs_grad(c) for c in sibs) \
+                or plan.grad.get(self.parent) is None:
+            return False
+        edge = 0                   # (the slices tile the parent's features: no gap, no overlap)
+        for lo, hi in sorted((c.lo, c.hi) for c in sibs):
+            if lo != edge:
+                return False
+            edge = hi
+        return edge == self.parent.shape['f']
+
     def _plan_alloc(self, plan):
-        if plan.needs_grad(self):
-            raise NotImplementedError(
-                "split: part '%s' needs a gradient (trainable parameters upstream of '%s', on the "
-                "loss path); the HIP hot path splits targets and other inputs only"
-                % (self.name, self.parent.name))
         src = plan.out.get(self.parent)
+        if plan.needs_grad(self):
+            if src is None or not self._grad_view_ok(plan):
+                raise NotImplementedError(
+                    "split: part '%s' needs a gradient (trainable parameters upstream of '%s', on "
+                    "the loss path); the HIP hot path splits targets and other inputs, and the "
+                    "mu / log_sig pair of a GaussianRV" % (self.name, self.parent.name))
+            plan.grad[self] = plan.grad[self.parent][:, self.lo:self.hi]
         if src is None:
             raise NotImplementedError("split: the output of '%s' is not materialised by the plan"
                                       % (self.parent.name,))
@@ -615,15 +638,16 @@ class SplitPart(Node):
         pass
 
     def _plan_bwd(self, plan):
-        pass
+        if self in plan.grad:
+            plan._grad_written.add(id(self.parent))     # (its gradient buffer holds this slice)
 
 
 def split(node, axis='f', index=None, n_out=None, strip_singleton_dims=False, name='split'):
     """node_basic.py:1335-1398: cut ``node`` along ``axis`` into ``n_out`` equal parts, or at the
     positions ``index``; returns a tuple of nodes.  ``name``: one name (made unique per part) or a
     list with one name per part.  The HIP hot path splits along ``'f'`` only, each part a view
-    (``SplitPart``); ``strip_singleton_dims`` and parts that need a gradient raise
-    NotImplementedError."""
+    (``SplitPart``); ``strip_singleton_dims`` raises NotImplementedError, and so do parts that
+    need a gradient, except the mu / log_sig pair of a ``GaussianRV`` (``SplitPart._grad_view_ok``)."""
     shape = node.shape
     tags = list(shape.tags)
     if isinstance(axis, str):

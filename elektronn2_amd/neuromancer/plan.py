@@ -91,6 +91,10 @@ class Plan(object):
         # issues the tick and the gate launches
         self._drop_nodes = [n for n in self.nodes if getattr(n, 'dropout_rate', None) is not None]
         self._drop_ids = set(id(n) for n in self._drop_nodes)
+        # GaussianRV nodes (various.py) draw from the same generator: a plan that has one issues
+        # the tick too -- ONE per step, whichever of the two kinds it holds
+        self._rv_nodes = [n for n in self.nodes if type(n).__name__ == 'GaussianRV']
+        self._rng_nodes = self._drop_nodes + self._rv_nodes
         # parameters that more than one node of this plan reads (w=<other>.w, ...): their gradient
         # slot receives several contributions per step ("Shared parameters")
         users = {}
@@ -265,7 +269,9 @@ class Plan(object):
         """the ``stream`` word of the node's gate launches: its ordinal among the MODEL's dropout
         nodes (fixed at plan build; the same in every plan of the model), plus the rank's offset
         in a data-parallel group (parallel.dropout_stream; read when the launches are issued --
-        the step is issued and captured again when data parallelism is switched on, _dp_key)"""
+        the step is issued and captured again when data parallelism is switched on, _dp_key).
+        The model's GaussianRV nodes are numbered behind its dropout nodes: no two random nodes of
+        a model share a stream."""
         from .. import parallel
         return parallel.dropout_stream(self._drop_ordinal[node], self.model.dp_rank())
 
@@ -552,9 +558,10 @@ class Plan(object):
         self._pack_rows_done = False
         self._img_stride = {}        # id(packed image) -> floats per row it is packed with (absent: formula)
         self.model.ensure_arena(self.ctx)
-        order = dict((id(n), i) for i, n in enumerate(self.model.dropout_nodes()))
-        self._drop_ordinal = dict((n, order[id(n)]) for n in self._drop_nodes)
-        if self._drop_nodes:
+        order = dict((id(n), i) for i, n in enumerate(self.model.dropout_nodes()
+                                                      + self.model.gaussian_rv_nodes()))
+        self._drop_ordinal = dict((n, order[id(n)]) for n in self._rng_nodes)
+        if self._rng_nodes:
             self.model.dropout_state_dev()       # (allocates: before any capture)
         with torch.cuda.stream(self.stream):
             # the static input buffers of all Input nodes are slices of ONE allocation (each
@@ -826,7 +833,7 @@ class Plan(object):
         the captured optimiser still divided by it)."""
         m = self.model
         # (a plan with dropout nodes has the rank in its launch arguments: dropout_stream)
-        rank = (m.dp_rank(),) if self._drop_nodes else ()
+        rank = (m.dp_rank(),) if self._rng_nodes else ()
         if not self.training:
             return (1,) + rank
         return (m.dp_world(), bool(getattr(m, '_dp_weighted', False)), bool(getattr(m, '_dp_force', False)),
@@ -1026,10 +1033,11 @@ class Plan(object):
         """the launches of segment i: (the step's prologue) + (the dropout tick) + (batched zero
         fills) + the segment"""
         ctx = self.ctx
-        if i == 0 and self._drop_nodes:
+        if i == 0 and self._rng_nodes:
             # once per step, in its first segment and in front of every gate launch, which read
             # the counter it leaves: each replay of the captured step (each of the k steps of a
             # run_steps graph) draws new gates, forward and backward of one step the same
+            # (likewise the noise of the GaussianRV nodes)
             ctx.dropout_tick(self.model.dropout_state_dev())
         if i == 0 and (self._ring is not None or self._hist is not None):
             # ONE launch: this step's batch out of the ring, the previous step's loss into the history

@@ -1221,6 +1221,55 @@ int e2_beta_nll_bwd(e2_ctx*, const e2_tensor5* mode, const e2_tensor5* conc,
                     const e2_tensor5* target, const float* coef, const e2_tensor5* dmode,
                     const e2_tensor5* dconc, int accumulate);
 
+/* ---- GaussianRV and its AEVB prior (csrc/gauss_rv.hip; various.py:32-106 GaussianRV, 111-151
+ *      GaussianAEVBPrior, n_samples = 0) ------------------------------------------------------
+ * The reference draws eps = rng.normal(mu.shape) from a Theano stream seeded with the wall clock
+ * (various.py:61-83) and lets T.grad keep it for the backward pass.  Here eps is a pure function
+ * of (seed, counter, stream, element index) on the generator of the dropout contract above, so
+ * that the backward pass REGENERATES it; no noise is ever stored.  The noise contract (tests
+ * restate it in NumPy float64):
+ *
+ *   j  = row-major index of the element (64-bit) in the LOGICAL dense shape (n, c, d, h, w) of
+ *        the mu view; q = j >> 2
+ *   (w0, w1, w2, w3) = philox4x32_10(ctr = (lo32(q), hi32(q), stream, counter),
+ *                                    key = (lo32(seed), hi32(seed)))            -- as in dropout
+ *   ua = ((w0 >> 8) + 1) * 2^-24  in (0, 1]       ub = (w1 >> 8) * 2^-24  in [0, 1)
+ *   r  = sqrt(-2 ln ua)
+ *   eps[4q + 0] = r cos(2 pi ub),   eps[4q + 1] = r sin(2 pi ub)
+ *   eps[4q + 2], eps[4q + 3]: the same from (w2, w3)
+ *
+ * Both uniforms are exact in f32.  One Philox block gives the four normals of one quad: a
+ * thread's 16-byte store is fed by exactly one block.  j depends on the logical shape alone:
+ * never on strides or launch geometry.
+ *   state   the four device words of the dropout launches (seed lo / hi, counter, unused), read
+ *           when the kernel runs; e2_dropout_tick advances it -- there is no second counter
+ *   stream  a launch argument; must differ from every dropout stream of the model
+ * e2_gaussrv_fwd: out = mu + exp(log_sig) * eps; out may alias neither input.
+ * e2_gaussrv_bwd: dmu (=|+=) dout;  dlog_sig (=|+=) dout * eps * exp(log_sig), eps of the same
+ *   (state, stream).
+ * e2_aevb_prior_fwd: the slab rows of e2_loss_fwd -- (S1, elements, 0, 0) per work-group,
+ *   e2_loss_partials(mu) rows, plain 16-byte stores, no atomics, bit-reproducible -- with S1 the
+ *   work-group's sum of 0.5 (mu^2 + exp(2 log_sig) - 1 - 2 log_sig).  The term enters e2_loss_mix,
+ *   unchanged, under a GAUSS_NLL-kind descriptor (a plain mean: L = S1 / n_tot, coef = mix /
+ *   (K n_tot)), as the mean of a loss map does.
+ * e2_aevb_prior_bwd: dmu (=|+=) coef[0] * mu;  dlog_sig (=|+=) coef[0] * (exp(2 log_sig) - 1);
+ *   coef: the DEVICE scalar the mix wrote.
+ * All views of a call are strided 5-D views of identical sizes.  A gradient view may be NULL (not
+ * wanted), not both; each has its own accumulate flag (!= 0 adds to what the view holds): both
+ * parents are network branches and either may already hold another consumer's gradient.  Refused
+ * with a message: views of different sizes, a NULL state, both gradient views NULL, a channel
+ * (d h w) of 2^31 elements or more.  One thread moves four consecutive j with one 16-byte access
+ * per view where they lie in one 16-byte aligned row piece; nothing outside a view is read or
+ * written.  All arithmetic is f32, in either MFMA mode. */
+int e2_gaussrv_fwd(e2_ctx*, const e2_tensor5* mu, const e2_tensor5* log_sig,
+                   const e2_tensor5* out, const void* state, uint32_t stream);
+int e2_gaussrv_bwd(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* log_sig,
+                   const e2_tensor5* dmu, const e2_tensor5* dlog_sig, int acc_mu, int acc_sig,
+                   const void* state, uint32_t stream);
+int e2_aevb_prior_fwd(e2_ctx*, const e2_tensor5* mu, const e2_tensor5* log_sig, float* partials);
+int e2_aevb_prior_bwd(e2_ctx*, const e2_tensor5* mu, const e2_tensor5* log_sig, const float* coef,
+                      const e2_tensor5* dmu, const e2_tensor5* dlog_sig, int acc_mu, int acc_sig);
+
 #ifdef __cplusplus
 }
 #endif
