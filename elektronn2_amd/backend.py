@@ -237,6 +237,11 @@ def _load():
         "e2_dense_fwd": (C.c_int, [vp, fp, fp, fp, i, i, i]),
         "e2_dense_dgrad": (C.c_int, [vp, fp, fp, fp, i, i, i, i]),
         "e2_dense_wgrad": (C.c_int, [vp, fp, fp, fp, i, i, i, i]),
+        "e2_dense_gemm_workspace_bytes": (sz, [i, i, i, i]),
+        "e2_dense_gemm_choice": (C.c_int, [i, i, i, i, i, C.POINTER(C.c_int)]),
+        "e2_dense_gemm_fwd": (C.c_int, [vp, vp, C.c_int64, fp, vp, C.c_int64, i, i, i, i, vp, sz]),
+        "e2_dense_gemm_dgrad": (C.c_int, [vp, vp, C.c_int64, fp, vp, C.c_int64, i, i, i, i, i, vp, sz]),
+        "e2_dense_gemm_wgrad": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, fp, i, i, i, i, i, vp, sz]),
         "e2_batchnorm_act_fwd": (C.c_int, [vp, P5, fp, fp, fp, fp, i, i, i, P5, fp]),
         "e2_batchnorm_act_bwd": (C.c_int, [vp, P5, P5, fp, fp, fp, i, i, P5, fp, fp]),
         "e2_get_mfma_dtype": (C.c_int, [vp]),
@@ -363,6 +368,16 @@ def _fp(t: Optional[torch.Tensor]):
         return None
     if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
         raise TypeError("expected a contiguous float32 GPU tensor")
+    return C.c_void_p(t.data_ptr())
+
+
+DENSE_OP = {"fwd": 0, "dgrad": 1, "wgrad": 2}       # e2_dense_gemm_choice
+
+
+def _rows(t: torch.Tensor):
+    """a 2-D float32 device view whose rows are dense (any row pitch): its first element"""
+    if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise TypeError("expected a 2-D float32 GPU view with unit column stride")
     return C.c_void_p(t.data_ptr())
 
 
@@ -1360,6 +1375,54 @@ class Context:
         n, k = x.shape
         _chk(_lib.e2_dense_wgrad(self.h, _fp(x), _fp(dy), _fp(dw), n, k, dy.shape[1],
                                  int(accumulate)), "e2_dense_wgrad")
+
+    # ---- the same products on the matrix cores (csrc/dense_gemm.hip) ---------------------
+    @staticmethod
+    def dense_gemm_workspace_bytes(n, k, m, splits=0):
+        """bytes of the workspace the three dense_gemm_* calls on (n, k, m) need at most"""
+        return int(_lib.e2_dense_gemm_workspace_bytes(int(n), int(k), int(m), int(splits)))
+
+    @staticmethod
+    def dense_gemm_choice(op, n, k, m, splits=0):
+        """what 'fwd' / 'dgrad' / 'wgrad' on (n, k, m) would run: dict(tile=(rows, columns), tiles,
+        splits, per (k-steps of 4 k per split), limit (the most splits a caller may ask for))"""
+        out = (C.c_int * 6)()
+        _chk(_lib.e2_dense_gemm_choice(DENSE_OP[op], int(n), int(k), int(m), int(splits), out),
+             "e2_dense_gemm_choice")
+        return dict(tile=(out[0], out[1]), tiles=out[2], splits=out[3], per=out[4], limit=out[5])
+
+    def dense_gemm_fwd(self, x, w, y, splits=0, ws=None):
+        """y (n, m) = x (n, k) . w (k, m); x, y: 2-D views with unit column stride (any row
+        pitch), w contiguous; ws: float32 workspace (None: the context's own)"""
+        n, k = x.shape
+        m = w.shape[1]
+        ws, nb = self._dense_ws(ws, n, k, m, splits)
+        _chk(_lib.e2_dense_gemm_fwd(self.h, _rows(x), x.stride(0), _fp(w), _rows(y), y.stride(0),
+                                    n, k, m, int(splits), ws, nb), "e2_dense_gemm_fwd")
+
+    def dense_gemm_dgrad(self, dy, w, dx, accumulate=False, splits=0, ws=None):
+        n, m = dy.shape
+        k = w.shape[0]
+        ws, nb = self._dense_ws(ws, n, k, m, splits)
+        _chk(_lib.e2_dense_gemm_dgrad(self.h, _rows(dy), dy.stride(0), _fp(w), _rows(dx),
+                                      dx.stride(0), n, k, m, int(accumulate), int(splits), ws, nb),
+             "e2_dense_gemm_dgrad")
+
+    def dense_gemm_wgrad(self, x, dy, dw, accumulate=False, splits=0, ws=None):
+        n, k = x.shape
+        m = dy.shape[1]
+        ws, nb = self._dense_ws(ws, n, k, m, splits)
+        _chk(_lib.e2_dense_gemm_wgrad(self.h, _rows(x), x.stride(0), _rows(dy), dy.stride(0),
+                                      _fp(dw), n, k, m, int(accumulate), int(splits), ws, nb),
+             "e2_dense_gemm_wgrad")
+
+    def _dense_ws(self, ws, n, k, m, splits):
+        if ws is None:
+            nb = self.dense_gemm_workspace_bytes(n, k, m, splits)
+            if not nb:
+                return None, 0
+            ws = self.workspace("dense_gemm", nb)
+        return C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size()
 
     def batchnorm_act_fwd(self, x, gamma, bias, run_mean, run_std, train, update_running, act,
                           out, save=None):

@@ -1183,9 +1183,18 @@ class Conv(NeuralLayer):
 class Perceptron(NeuralLayer):
     """Perceptron layer (neural.py:258-410): ``act((gamma / std) * dot(x, w) + b - ...)``;
     ``w`` has the reference's (n_in, n_f) shape; ``flatten=True`` joins every non-batch axis
-    of the parent (C order).  Device side: csrc/dense_bn.hip."""
+    of the parent (C order).  Device side: csrc/dense_bn.hip; the three dot products of a large
+    node run on the matrix cores (csrc/dense_gemm.hip, plan option ``dense_gemm``)."""
 
     _drop_per_feature = True      # size=(n_f,), broadcast over the batch (neural.py:391-397)
+    # option dense_gemm='auto': the MFMA GEMMs from this many multiply-adds per dot product
+    # (batch * n_in * n_f) on.  Above the largest dot of the nets the suite had before the GEMMs
+    # (config 1: 20 * 576 * 200), which therefore issue the launches they always did.
+    DENSE_GEMM_MIN_MACS = 2 ** 22
+    # ... the weight gradient, whose reduction is only the batch, from the smallest measured shape
+    # at which it beats the old kernel beyond the run-to-run spread (DESIGN.md section 27: at
+    # (32, 600, 256) it is one launch at the launch floor either way and the old one is 0.9 us ahead)
+    DENSE_GEMM_WGRAD_MIN_MACS = 128 * 784 * 512
 
     def __init__(self, parent, n_f, activation_func='relu',
                  flatten=False, batch_normalisation=False, dropout_rate=0,
@@ -1231,6 +1240,16 @@ class Perceptron(NeuralLayer):
     def _bn(self):
         return self.batch_normalisation in ('train', 'predict')
 
+    def dense_gemm_route(self, batch, option='auto', op='fwd'):
+        """does the product ``op`` ('fwd' / 'dgrad' / 'wgrad') of this node at ``batch`` run
+        csrc/dense_gemm.hip under the plan option ``dense_gemm`` = 'auto' / True / False?"""
+        if option == 'auto':
+            return int(batch) * self.w_sh[0] * self.w_sh[1] >= \
+                (self.DENSE_GEMM_WGRAD_MIN_MACS if op == 'wgrad' else self.DENSE_GEMM_MIN_MACS)
+        if option is True or option is False:
+            return option
+        raise ValueError("plan option dense_gemm is 'auto', True or False, not %r" % (option,))
+
     def _plan_alloc(self, plan):
         plan.alloc_out(self)
         plan.scratch[self, 'lin'] = plan.empty(plan.out_shape(self))
@@ -1240,6 +1259,10 @@ class Perceptron(NeuralLayer):
             plan.scratch[self, 'bn_save'] = plan.zeros_flat(2 * self.n_f)
             if not self._plain_act() and plan.training:
                 plan.scratch[self, 'pre'] = plan.empty(plan.out_shape(self))
+        if self.dense_gemm_route(plan.batch, plan.opt['dense_gemm']):
+            # one workspace for the split-K slabs of the node's three GEMMs (the largest need)
+            nb = plan.ctx.dense_gemm_workspace_bytes(plan.batch, self.w_sh[0], self.w_sh[1])
+            plan.scratch[self, 'gemm_ws'] = plan.empty_flat((nb + 3) // 4) if nb else None
 
     def _x2(self, plan, t):
         """the parent's buffer as the (batch, n_in) matrix"""
@@ -1250,8 +1273,12 @@ class Perceptron(NeuralLayer):
     def _plan_fwd(self, plan):
         ctx = plan.ctx
         lin = plan.scratch[self, 'lin']
-        ctx.dense_fwd(self._x2(plan, plan.out[self.parent]), plan.param(self.w),
-                      lin.reshape(lin.shape[0], -1))
+        if (self, 'gemm_ws') in plan.scratch:
+            ctx.dense_gemm_fwd(self._x2(plan, plan.out[self.parent]), plan.param(self.w),
+                               lin.reshape(lin.shape[0], -1), ws=plan.scratch[self, 'gemm_ws'])
+        else:
+            ctx.dense_fwd(self._x2(plan, plan.out[self.parent]), plan.param(self.w),
+                          lin.reshape(lin.shape[0], -1))
         if self._bn():
             train = self.batch_normalisation == 'train'
             pre = plan.scratch.get((self, 'pre'), plan.out[self])
@@ -1286,11 +1313,18 @@ class Perceptron(NeuralLayer):
             ctx.pool_bias_act_bwd(plan.grad[self], lin, plan.param(self.b), (1, 1, 1),
                                   self.activation_func, dlin, plan.pgrad(self.b))
         d2 = dlin.reshape(dlin.shape[0], -1)
-        ctx.dense_wgrad(self._x2(plan, plan.out[self.parent]), d2, plan.pgrad(self.w),
-                        accumulate=True)
+        gemm = (self, 'gemm_ws') in plan.scratch
+        kw = dict(ws=plan.scratch[self, 'gemm_ws']) if gemm else {}
+        dgrad = ctx.dense_gemm_dgrad if gemm else ctx.dense_dgrad
+        if gemm and self.dense_gemm_route(plan.batch, plan.opt['dense_gemm'], 'wgrad'):
+            ctx.dense_gemm_wgrad(self._x2(plan, plan.out[self.parent]), d2, plan.pgrad(self.w),
+                                 accumulate=True, **kw)
+        else:
+            ctx.dense_wgrad(self._x2(plan, plan.out[self.parent]), d2, plan.pgrad(self.w),
+                            accumulate=True)
         if plan.needs_grad(self.parent):
             dst, first = plan.grad_slot(self.parent)
-            ctx.dense_dgrad(d2, plan.param(self.w), self._x2(plan, dst), accumulate=not first)
+            dgrad(d2, plan.param(self.w), self._x2(plan, dst), accumulate=not first, **kw)
 
 
 class FragmentsToDense(Node):

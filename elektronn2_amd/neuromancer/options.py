@@ -22,6 +22,10 @@ def _tri(v):
     return None if v is None or str(v) == "" else _b(v)
 
 
+def _auto(v):
+    return "auto" if str(v).strip().lower() == "auto" else _b(v)
+
+
 # name: (environment variable, parser, default, what it does)
 SPEC = {
     "graph": ("E2_NO_GRAPH", lambda v: not _b(v), True,
@@ -90,6 +94,11 @@ SPEC = {
     "bf16_ahead_wgrad_only": ("E2_BF16_AHEAD_WGRAD_ONLY", _b, False, "... gradient images for the weight gradient alone"),
     "bf16_xkeep": ("E2_BF16_XKEEP", _b, True, "bf16 mode: the forward's channels-last copy of x serves the wgrad"),
     "bf16_wpack": ("E2_BF16_WPACK", str, "step", "'step': one filter-row pack launch per step; 'call': per launch"),
+    "dense_gemm": ("E2_DENSE_GEMM", _auto, "auto",
+                   "a Perceptron's three dot products on the MFMA GEMMs of csrc/dense_gemm.hip: True / False, "
+                   "'auto' = from 2**22 multiply-adds per product (batch * n_in * n_f) on, the weight gradient from "
+                   "128 * 784 * 512 on (measured: DESIGN.md section 27); below, the one-thread-per-output kernels "
+                   "of csrc/dense_bn.hip"),
     "dense_act_gib": ("E2_DENSE_ACT_GIB", float, 48.0, "activation budget of tiled dense prediction (GiB)"),
 }
 

@@ -985,6 +985,30 @@ int e2_dense_dgrad(e2_ctx*, const float* dy, const float* w, float* dx, int n, i
                    int accumulate);
 int e2_dense_wgrad(e2_ctx*, const float* x, const float* dy, float* dw, int n, int k, int m,
                    int accumulate);
+/* The same three products on the matrix cores (csrc/dense_gemm.hip; neural.py:258-410,
+ * computations.py:179-213 `dot` and its two gradients): one f32 16x16x4 MFMA GEMM core, operands
+ * staged in LDS, any positive n, k, m, no alignment asked of the caller.
+ *   ld*: row pitches in floats, at least the row length (a row block inside a wider buffer);
+ *        w (k x m) and dw (k x m) are dense.
+ *   splits: the reduction is dealt out to `splits` work-groups per output tile, which store partial
+ *        slabs into ws; a second launch adds them in a fixed order (and the base, with
+ *        accumulate).  No atomics: bit-reproducible for every split count.  0: the library
+ *        chooses (from the tile count and the 256 CUs of an MI355X); >= 1: honoured, or refused
+ *        when it exceeds ceil(reduction length / 4) (at most 1024).
+ *   ws:  splits slabs of the output (e2_dense_gemm_workspace_bytes: the largest need of the three
+ *        calls on (n, k, m) at this `splits`; 0 where nothing is split); may be NULL then.
+ * e2_dense_gemm_choice: what a call with these arguments would run -- op 0 fwd, 1 dgrad, 2 wgrad;
+ *   out6 = tile rows, tile columns, output tiles, splits, k-steps (4 k) per split, split limit. */
+size_t e2_dense_gemm_workspace_bytes(int n, int k, int m, int splits);
+int e2_dense_gemm_choice(int op, int n, int k, int m, int splits, int* out6);
+int e2_dense_gemm_fwd(e2_ctx*, const float* x, int64_t ldx, const float* w, float* y, int64_t ldy,
+                      int n, int k, int m, int splits, void* ws, size_t ws_bytes);
+int e2_dense_gemm_dgrad(e2_ctx*, const float* dy, int64_t lddy, const float* w, float* dx,
+                        int64_t lddx, int n, int k, int m, int accumulate, int splits, void* ws,
+                        size_t ws_bytes);
+int e2_dense_gemm_wgrad(e2_ctx*, const float* x, int64_t ldx, const float* dy, int64_t lddy,
+                        float* dw, int n, int k, int m, int accumulate, int splits, void* ws,
+                        size_t ws_bytes);
 /* Batch normalisation + bias + activation (neural.py:352-378 Perceptron, 681-711 Conv; applied
  * to the pooled conv output / the dot product):
  *   train != 0: mean, std = statistics of x over every axis but the channel (population std,
