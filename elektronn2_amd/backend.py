@@ -244,6 +244,10 @@ def _load():
         "e2_dense_gemm_wgrad": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, fp, i, i, i, i, i, vp, sz]),
         "e2_batchnorm_act_fwd": (C.c_int, [vp, P5, fp, fp, fp, fp, i, i, i, P5, fp]),
         "e2_batchnorm_act_bwd": (C.c_int, [vp, P5, P5, fp, fp, fp, i, i, P5, fp, fp]),
+        "e2_batchnorm_wide_workspace_bytes": (sz, [i, i, i, i, i, i]),
+        "e2_batchnorm_wide_choice": (C.c_int, [i, i, i, i, i, i, C.POINTER(C.c_int)]),
+        "e2_batchnorm_wide_fwd": (C.c_int, [vp, P5, fp, fp, fp, fp, i, i, i, P5, fp, i, vp, sz]),
+        "e2_batchnorm_wide_bwd": (C.c_int, [vp, P5, P5, fp, fp, fp, i, i, P5, fp, fp, i, vp, sz]),
         "e2_get_mfma_dtype": (C.c_int, [vp]),
         "e2_dropout_fwd": (C.c_int, [vp, P5, P5, i, fp, vp, C.c_uint32]),
         "e2_dropout_bwd": (C.c_int, [vp, P5, P5, i, fp, vp, C.c_uint32]),
@@ -1436,6 +1440,44 @@ class Context:
                                        _fp(bias), _fp(save), int(bool(train)), ACT[act],
                                        C.byref(t5(dx)) if dx is not None else None,
                                        _fp(dgamma), _fp(dbias)), "e2_batchnorm_act_bwd")
+
+    # ---- the same pair over C x slabs work-groups (csrc/bn_wide.hip) ----------------------
+    @staticmethod
+    def batchnorm_wide_workspace_bytes(shape, splits=0):
+        """bytes of the workspace the two batchnorm_wide_* calls on an (n, c, d, h, w) tensor need"""
+        n, c, d, h, w = (int(v) for v in shape)
+        return int(_lib.e2_batchnorm_wide_workspace_bytes(n, c, d, h, w, int(splits)))
+
+    @staticmethod
+    def batchnorm_wide_choice(shape, splits=0):
+        """how an (n, c, d, h, w) tensor would be cut: dict(slabs per channel, rows of the largest
+        slab, work_groups of a launch, limit (the most slabs a caller may ask for))"""
+        n, c, d, h, w = (int(v) for v in shape)
+        out = (C.c_int * 4)()
+        _chk(_lib.e2_batchnorm_wide_choice(n, c, d, h, w, int(splits), out), "e2_batchnorm_wide_choice")
+        return dict(slabs=out[0], rows=out[1], work_groups=out[2], limit=out[3])
+
+    def batchnorm_wide_fwd(self, x, gamma, bias, run_mean, run_std, train, update_running, act,
+                           out, save=None, splits=0, ws=None):
+        ws, nb = self._bn_ws(ws, x.shape, splits)
+        _chk(_lib.e2_batchnorm_wide_fwd(self.h, C.byref(t5(x)), _fp(gamma), _fp(bias),
+                                        _fp(run_mean), _fp(run_std), int(bool(train)),
+                                        int(bool(update_running)), ACT[act], C.byref(t5(out)),
+                                        _fp(save), int(splits), ws, nb), "e2_batchnorm_wide_fwd")
+
+    def batchnorm_wide_bwd(self, dout, x, gamma, bias, save, train, act, dx, dgamma, dbias,
+                           splits=0, ws=None):
+        ws, nb = self._bn_ws(ws, x.shape, splits)
+        _chk(_lib.e2_batchnorm_wide_bwd(self.h, C.byref(t5(dout)), C.byref(t5(x)), _fp(gamma),
+                                        _fp(bias), _fp(save), int(bool(train)), ACT[act],
+                                        C.byref(t5(dx)) if dx is not None else None,
+                                        _fp(dgamma), _fp(dbias), int(splits), ws, nb),
+             "e2_batchnorm_wide_bwd")
+
+    def _bn_ws(self, ws, shape, splits):
+        if ws is None:            # the context's own (a refused shape: the call itself reports it)
+            ws = self.workspace("bn_wide", max(self.batchnorm_wide_workspace_bytes(shape, splits), 4))
+        return C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size()
 
     def set_tiling(self, kind, cfg):
         """force the tiling of the following 'igemm' ("MT,NT,CC,SK": conv fwd / dgrad /

@@ -14,7 +14,8 @@ bookkeeping (elektronn2/neuromancer/neural.py), executing through libe2hip.so.
 
 2-D convolutions ('b,f,y,x', BASELINE config 1 = examples/mnist.py) run through the same
 kernels with a unit z axis; batch normalisation ('train' / 'predict', neural.py:681-711)
-has its own kernel (csrc/dense_bn.hip).
+has its own kernels: one work-group per channel (csrc/dense_bn.hip) for small nodes, channels cut
+into slabs over the whole card (csrc/bn_wide.hip, plan option ``bn_wide``) for conv-sized ones.
 
 Dropout (``dropout_rate=`` of Conv / UpConv / Perceptron, neural.py:246-249,391-397,714-720,
 1064-1070) is the last thing a node does to its output: one launch in place on the node's
@@ -124,6 +125,41 @@ class NeuralLayer(Node):
         """the activation to hand to the node's own kernels: its own when they can fuse it,
         'lin' when the act pair follows"""
         return self.activation_func if self._plain_act() else 'lin'
+
+    # option bn_wide='auto': csrc/bn_wide.hip from this many elements per channel (batch * spatial
+    # extent of the normalised tensor) on: the smallest measured count at which its forward and its
+    # backward both beat the one-work-group-per-channel kernels beyond the run-to-run spread
+    # (DESIGN.md section 28: 16384, 3.3 x and 3.5 x at spreads of 7 % and 5 %) among the counts
+    # above every batch-norm node of the nets the suite had before it (config 1: 20 * 24 * 24),
+    # which therefore issue the launches they always did.
+    BN_WIDE_MIN_COUNT = 2 ** 14
+
+    def _bn_wide(self, plan, shape):
+        """does the batch normalisation of this node, acting on a tensor of the 5-D ``shape``, run
+        csrc/bn_wide.hip under the plan option ``bn_wide`` = 'auto' / True / False?"""
+        option = plan.opt['bn_wide']
+        if option == 'auto':
+            n, _, d, h, w = (int(v) for v in shape)
+            return n * d * h * w >= self.BN_WIDE_MIN_COUNT
+        if option is True or option is False:
+            return option
+        raise ValueError("plan option bn_wide is 'auto', True or False, not %r" % (option,))
+
+    def _bn_alloc(self, plan):
+        """what the batch-norm pair of this node keeps: the statistics the forward used and, on the
+        wide route, one workspace for the slab records of both calls"""
+        plan.scratch[self, 'bn_save'] = plan.zeros_flat(2 * self.n_f)
+        shape = plan.out_shape(self)
+        if self._bn_wide(plan, shape):
+            nb = plan.ctx.batchnorm_wide_workspace_bytes(shape)
+            plan.scratch[self, 'bn_ws'] = plan.empty_flat((nb + 3) // 4)
+
+    def _bn_calls(self, plan):
+        """the Context pair this node's batch norm runs and the keyword arguments that go with it"""
+        ws = plan.scratch.get((self, 'bn_ws'))
+        if ws is not None:
+            return plan.ctx.batchnorm_wide_fwd, plan.ctx.batchnorm_wide_bwd, dict(ws=ws)
+        return plan.ctx.batchnorm_act_fwd, plan.ctx.batchnorm_act_bwd, {}
 
     def _drop_fwd(self, plan):
         """dropout, the last thing a node does to its output (neural.py:712-722): in place on
@@ -706,7 +742,7 @@ class Conv(NeuralLayer):
                 plan.scratch[self, 'lin'] = plan.empty(plan.out_shape(self))
                 if plan.training:
                     plan.scratch[self, 'dlin'] = plan.empty(plan.out_shape(self))
-            plan.scratch[self, 'bn_save'] = plan.zeros_flat(2 * self.n_f)
+            self._bn_alloc(plan)
         if not self._plain_act() and plan.training:
             # what e2_act_bwd reads: the batch-normalised / pooled pre-activation (an un-pooled
             # conv without batch norm has it in `y` already)
@@ -888,10 +924,11 @@ class Conv(NeuralLayer):
             # the running statistics are extra updates of the OPTIMISER's step function
             # (model.py:180-192), not of loss / prediction / gradient functions
             pre = plan.scratch.get((self, 'pre'), plan.out[self])
-            ctx.batchnorm_act_fwd(lin, plan.param(self.gamma), plan.param(self.b),
-                                  plan.param(self.mean), plan.param(self.std), train,
-                                  train and plan.updates_params(), self._lin_act(),
-                                  pre, plan.scratch[self, 'bn_save'])
+            bn_fwd, _, kw = self._bn_calls(plan)
+            bn_fwd(lin, plan.param(self.gamma), plan.param(self.b),
+                   plan.param(self.mean), plan.param(self.std), train,
+                   train and plan.updates_params(), self._lin_act(),
+                   pre, plan.scratch[self, 'bn_save'], **kw)
             if not self._plain_act():
                 ctx.act_fwd(pre, None, self.activation_func, plan.out[self])
             return
@@ -974,11 +1011,12 @@ class Conv(NeuralLayer):
             if not self._plain_act():          # in place on the output gradient
                 ctx.act_bwd(plan.grad[self], plan.scratch[self, 'pre'], None, self.activation_func,
                             plan.grad[self], None)
-            ctx.batchnorm_act_bwd(plan.grad[self], lin, plan.param(self.gamma),
-                                  plan.param(self.b), plan.scratch[self, 'bn_save'], train,
-                                  self._lin_act(), dlin,
-                                  plan.pgrad(self.gamma) if self.gamma.apply_train else None,
-                                  plan.pgrad(self.b))
+            _, bn_bwd, kw = self._bn_calls(plan)
+            bn_bwd(plan.grad[self], lin, plan.param(self.gamma),
+                   plan.param(self.b), plan.scratch[self, 'bn_save'], train,
+                   self._lin_act(), dlin,
+                   plan.pgrad(self.gamma) if self.gamma.apply_train else None,
+                   plan.pgrad(self.b), **kw)
             if pooled:
                 ctx.maxpool3d_bwd(dlin, plan.scratch[self, 'y'], self._p3, dy)
         elif not self._plain_act():
@@ -1256,7 +1294,7 @@ class Perceptron(NeuralLayer):
         if plan.training:
             plan.scratch[self, 'dlin'] = plan.empty(plan.out_shape(self))
         if self._bn():
-            plan.scratch[self, 'bn_save'] = plan.zeros_flat(2 * self.n_f)
+            self._bn_alloc(plan)
             if not self._plain_act() and plan.training:
                 plan.scratch[self, 'pre'] = plan.empty(plan.out_shape(self))
         if self.dense_gemm_route(plan.batch, plan.opt['dense_gemm']):
@@ -1282,10 +1320,11 @@ class Perceptron(NeuralLayer):
         if self._bn():
             train = self.batch_normalisation == 'train'
             pre = plan.scratch.get((self, 'pre'), plan.out[self])
-            ctx.batchnorm_act_fwd(lin, plan.param(self.gamma), plan.param(self.b),
-                                  plan.param(self.mean), plan.param(self.std), train,
-                                  train and plan.updates_params(), self._lin_act(),
-                                  pre, plan.scratch[self, 'bn_save'])
+            bn_fwd, _, kw = self._bn_calls(plan)
+            bn_fwd(lin, plan.param(self.gamma), plan.param(self.b),
+                   plan.param(self.mean), plan.param(self.std), train,
+                   train and plan.updates_params(), self._lin_act(),
+                   pre, plan.scratch[self, 'bn_save'], **kw)
             if not self._plain_act():
                 ctx.act_fwd(pre, None, self.activation_func, plan.out[self])
         elif not self._plain_act():
@@ -1301,11 +1340,12 @@ class Perceptron(NeuralLayer):
             if not self._plain_act():          # in place on the output gradient
                 ctx.act_bwd(plan.grad[self], plan.scratch[self, 'pre'], None, self.activation_func,
                             plan.grad[self], None)
-            ctx.batchnorm_act_bwd(plan.grad[self], lin, plan.param(self.gamma),
-                                  plan.param(self.b), plan.scratch[self, 'bn_save'],
-                                  self.batch_normalisation == 'train', self._lin_act(),
-                                  dlin, plan.pgrad(self.gamma) if self.gamma.apply_train else None,
-                                  plan.pgrad(self.b))
+            _, bn_bwd, kw = self._bn_calls(plan)
+            bn_bwd(plan.grad[self], lin, plan.param(self.gamma),
+                   plan.param(self.b), plan.scratch[self, 'bn_save'],
+                   self.batch_normalisation == 'train', self._lin_act(),
+                   dlin, plan.pgrad(self.gamma) if self.gamma.apply_train else None,
+                   plan.pgrad(self.b), **kw)
         elif not self._plain_act():
             ctx.act_bwd(plan.grad[self], lin, plan.param(self.b), self.activation_func, dlin,
                         plan.pgrad(self.b))
@@ -1427,7 +1467,7 @@ class UpConv(Conv):
             # batch norm acts on the bare upconvolution (neural.py:1032-1061): the GEMM leaves it
             # in `lin`, e2_batchnorm_act_fwd carries it to the output (or to `pre`)
             plan.scratch[self, 'lin'] = plan.empty(plan.out_shape(self))
-            plan.scratch[self, 'bn_save'] = plan.zeros_flat(2 * self.n_f)
+            self._bn_alloc(plan)
             if plan.training:
                 plan.scratch[self, 'dlin'] = plan.empty(plan.out_shape(self))
         xs = plan.out_shape(self.parent)
@@ -1485,10 +1525,11 @@ class UpConv(Conv):
         plan.tuned('igemm', sig, cands, run)
         if bn:
             train = self.batch_normalisation == 'train'
-            plan.ctx.batchnorm_act_fwd(dst, plan.param(self.gamma), plan.param(self.b),
-                                       plan.param(self.mean), plan.param(self.std), train,
-                                       train and plan.updates_params(), self._lin_act(),
-                                       pre, plan.scratch[self, 'bn_save'])
+            bn_fwd, _, kw = self._bn_calls(plan)
+            bn_fwd(dst, plan.param(self.gamma), plan.param(self.b),
+                   plan.param(self.mean), plan.param(self.std), train,
+                   train and plan.updates_params(), self._lin_act(),
+                   pre, plan.scratch[self, 'bn_save'], **kw)
         if not self._plain_act():
             plan.ctx.act_fwd(pre, None, self.activation_func, plan.out[self])
 
@@ -1514,11 +1555,12 @@ class UpConv(Conv):
         if self._bn():
             # once, outside `run` (it ADDS to dgamma / dbias); the GEMMs then see the gradient
             # of the bare upconvolution: no activation, no bias gradient of their own
-            ctx.batchnorm_act_bwd(dout, plan.scratch[self, 'lin'], plan.param(self.gamma),
-                                  plan.param(self.b), plan.scratch[self, 'bn_save'],
-                                  self.batch_normalisation == 'train', act,
-                                  plan.scratch[self, 'dlin'],
-                                  plan.pgrad(self.gamma) if self.gamma.apply_train else None, dbias)
+            _, bn_bwd, kw = self._bn_calls(plan)
+            bn_bwd(dout, plan.scratch[self, 'lin'], plan.param(self.gamma),
+                   plan.param(self.b), plan.scratch[self, 'bn_save'],
+                   self.batch_normalisation == 'train', act,
+                   plan.scratch[self, 'dlin'],
+                   plan.pgrad(self.gamma) if self.gamma.apply_train else None, dbias, **kw)
             dout, act, dbias = plan.scratch[self, 'dlin'], 'lin', None
         # a parameter shared with another node: its slot may hold that node's contribution, which
         # an overwriting call would wipe -- this node's goes to buffers of its own (overwritten:

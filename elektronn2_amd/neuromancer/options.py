@@ -99,6 +99,10 @@ SPEC = {
                    "'auto' = from 2**22 multiply-adds per product (batch * n_in * n_f) on, the weight gradient from "
                    "128 * 784 * 512 on (measured: DESIGN.md section 27); below, the one-thread-per-output kernels "
                    "of csrc/dense_bn.hip"),
+    "bn_wide": ("E2_BN_WIDE", _auto, "auto",
+                "batch normalisation of Conv / UpConv / Perceptron on the C x slabs work-groups of "
+                "csrc/bn_wide.hip: True / False, 'auto' = from NeuralLayer.BN_WIDE_MIN_COUNT elements per channel "
+                "on (measured: DESIGN.md section 28); below, one work-group per channel (csrc/dense_bn.hip)"),
     "dense_act_gib": ("E2_DENSE_ACT_GIB", float, 48.0, "activation budget of tiled dense prediction (GiB)"),
 }
 

@@ -1026,6 +1026,29 @@ int e2_batchnorm_act_fwd(e2_ctx*, const e2_tensor5* x, const float* gamma, const
 int e2_batchnorm_act_bwd(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* x,
                          const float* gamma, const float* bias, const float* save, int train,
                          int act, const e2_tensor5* dx, float* dgamma, float* dbias);
+/* The same pair for conv-sized tensors (csrc/bn_wide.hip; neural.py:352-378, 681-711): a channel is
+ * cut into `slabs` runs of whole rows (a row: the w floats at one (n, z, y)), the grid is
+ * c x slabs work-groups, rows move as 16-byte accesses where they are aligned.  The pair above
+ * gives a channel to one work-group and stays the route of small nodes.  Same arguments, same
+ * refusals, same formulas (the variance from squares about each 4096-element tile's own mean,
+ * combined in a fixed order: no atomics, bit-reproducible, independent of strides).
+ *   splits: 0: the library chooses the slabs (a few work-groups for each of the 256 CUs of an
+ *        MI355X, at most 64 per channel, none below 8192 elements); >= 1: honoured, or refused
+ *        above `limit` = min(rows of a channel, 1024).
+ *   ws:  e2_batchnorm_wide_workspace_bytes at this shape and `splits` (the larger need of the two
+ *        calls); never cleared by the caller: every word read was stored by the launch before.
+ *        A predict-mode forward needs none.
+ * e2_batchnorm_wide_choice: out4 = slabs, rows of the largest slab, work-groups, limit. */
+size_t e2_batchnorm_wide_workspace_bytes(int n, int c, int d, int h, int w, int splits);
+int e2_batchnorm_wide_choice(int n, int c, int d, int h, int w, int splits, int* out4);
+int e2_batchnorm_wide_fwd(e2_ctx*, const e2_tensor5* x, const float* gamma, const float* bias,
+                          float* run_mean, float* run_std, int train, int update_running,
+                          int act, const e2_tensor5* out, float* save, int splits, void* ws,
+                          size_t ws_bytes);
+int e2_batchnorm_wide_bwd(e2_ctx*, const e2_tensor5* dout, const e2_tensor5* x,
+                          const float* gamma, const float* bias, const float* save, int train,
+                          int act, const e2_tensor5* dx, float* dgamma, float* dbias, int splits,
+                          void* ws, size_t ws_bytes);
 
 /* ---- dropout (neural.py:246-249 the rate parameter; 391-397 Perceptron: one gate per output
  *      feature; 714-720 Conv and 1064-1070 UpConv: one gate per output element; the last thing a
